@@ -19,23 +19,35 @@ reduction and (C4 job) the hand-over of records to rank 0.
                    value = aggregate batch-64 steps/s over all ranks.
   --scaling strong the ONE batch of 64 fields is cut across the ranks (64/N
                    fields per GPU); value = steps/s of that batch (north_star's
-                   ">= 7x at 8 GPUs" figure).  A weak-scaling run reports the
-                   strong-scaling measurement beside it (`strong_scaling`), so
-                   one `--gpus N` run holds both.
+                   ">= 7x at 8 GPUs" figure).  A weak-scaling `--full` run
+                   reports the strong-scaling measurement beside it
+                   (`strong_scaling`), so one `--gpus N --full` run holds both.
 `c4_ensemble` is BASELINE configs[3]: the 512-sample McWilliams job (512^2, fp64,
 100 + 550 steps, 10 records x 4 fields) cut across the N ranks, with the
 un-hidden tail of the gather + D2H split out.
 
 Prints ONE JSON line (rank 0), under 8 KB, and nothing holding a brace after it on
-either stream (stderr is passed through a filter that replaces braces).  `value`
-is the median of `--regions` regions of K timed steps.  `roofline` is for the
-dominant kernel, measured with HIP events recorded by the library on the launch
-stream over K instrumented steps; `cpu_baseline` times the CPU oracle (a torch-CPU
-restatement of the reference's op sequence) on this host.  The secondary
-workloads (other solver configs, the SFNO model runs) are a separate process with
-a time limit (bench_secondary.py) started after the headline is measured; a few
-scalars of each are folded into the line, the full record goes to
-gpurun_out/bench_detail.json.
+either stream (stderr is passed through a filter that replaces braces).
+
+A plain run (`--gpus 1 --steps K --warmup W`) measures the headline and nothing
+else: set-up, W untimed steps, EXACTLY K timed steps between two fences, the
+outputs if `--dump-outputs DIR` is given, the line.  `value` = K / seconds of
+those steps (x N ranks for weak scaling), `ms_per_step` = seconds / K.
+`--dump-outputs DIR` writes what the timed path returned in its last step, the
+new state and dw/dt of forward(w, dt), as DIR/w.npy and DIR/dwdt.npy (see
+dump_outputs); the inputs depend on the arguments alone, so two builds can be
+compared output for output.
+
+`--full` adds everything else, as one run: `value` is then the median of
+`--regions` regions of K timed steps after `--preheat` untimed ones.  `roofline` is
+for the dominant kernel, measured with HIP events recorded by the library on the
+launch stream over K instrumented steps; `cpu_baseline` times the CPU oracle (a
+torch-CPU restatement of the reference's op sequence) on this host; then the
+`forward(w, dt, steps=K)` figure, the other scaling mode, the strong-scaling proxy,
+the HBM probe and the C4 job.  The secondary workloads (other solver configs, the
+SFNO model runs) are a separate process with a time limit (bench_secondary.py)
+started after the headline is measured; a few scalars of each are folded into the
+line, the full record goes to the detail file bench_detail.json (write_detail).
 """
 import argparse
 import ctypes
@@ -85,14 +97,29 @@ def parse(argv=None):
     ap.add_argument("--c4-only", action="store_true",
                     help="run ONLY the C4 ensemble job and print its JSON (what a multi-rank run starts as a separate job)")
     ap.add_argument("--c4-timeout", type=float, default=180.0, help="seconds the separate C4 job of a multi-rank run may take")
-    ap.add_argument("--regions", type=int, default=5, help="timed regions of W + K steps; value = the median region")
-    ap.add_argument("--preheat", type=int, default=20, help="untimed steps before the first region (clock ramp, caches)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: median of --regions regions after --preheat steps, instrumented "
+                         "per-kernel roofline, CPU baseline, fused-steps API, other scaling mode, strong-scaling proxy, HBM "
+                         "probe, C4 job, secondary workloads (bench_secondary.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--regions", type=int, default=None,
+                    help="timed regions of W + K steps; value = the median region (default 1; 5 with --full)")
+    ap.add_argument("--preheat", type=int, default=None,
+                    help="untimed steps before the first region (clock ramp, caches; default 0; 20 with --full)")
     ap.add_argument("--secondary-timeout", type=float, default=420.0,
                     help="seconds the separate job of secondary workloads (bench_secondary.py) may take")
     ap.add_argument("--host-only", action="store_true",
                     help="launcher / timing / reduction path only, on CPU over gloo with a no-op step (no kernels): "
                          "what the CPU test of the N-rank spawner runs")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.regions is None:
+        args.regions = 5 if args.full else 1
+    if args.preheat is None:
+        args.preheat = 20 if args.full else 0
+    return args
 
 
 def spawn_ranks(args, argv):
@@ -544,6 +571,50 @@ def write_detail(full):
     return None
 
 
+DUMP_SAMPLE = 1 << 20    # complex entries per output that --dump-outputs keeps (16 MiB per output in fp64)
+
+
+def dump_outputs(dirname, outputs):
+    """`--dump-outputs DIR`: each complex output as DIR/<name>.npy, shape (entries, 2) = real and imaginary parts, in the
+    run's real dtype (float64 or float32).  An output of more than DUMP_SAMPLE entries is written as a fixed sample of
+    them: flat index i * stride + offset_i for i < DUMP_SAMPLE, stride = entries // DUMP_SAMPLE, the offsets drawn from a
+    generator seeded with 0 -- the same shape always gives the same entries, so two runs with the same arguments compare
+    entry for entry.  Returns {name: shape} for the result line."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    shapes = {}
+    for name, t in outputs.items():
+        flat = torch.view_as_real(t.detach().contiguous()).reshape(-1, 2)
+        total = flat.shape[0]
+        if total > DUMP_SAMPLE:
+            stride = total // DUMP_SAMPLE
+            gen = torch.Generator().manual_seed(0)
+            idx = torch.arange(DUMP_SAMPLE, dtype=torch.int64) * stride + torch.randint(0, stride, (DUMP_SAMPLE,), generator=gen)
+            flat = flat.index_select(0, idx.to(flat.device))
+        arr = flat.cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+        shapes[name] = list(arr.shape)
+    return {"dir": dirname, "shapes": shapes, "of": {name: list(t.shape) for name, t in outputs.items()},
+            "sample": f"all entries up to {DUMP_SAMPLE}, else {DUMP_SAMPLE} at fixed seeded positions (bench.dump_outputs)"}
+
+
+def emit(out, detail, rank, real_stdout, use_dist, dist):
+    """Rank 0 writes THE line -- a plain run's record as it is; with --full (`detail` given) the composed line, the full
+    record going to the detail file -- then every rank leaves the process group."""
+    if rank == 0:
+        line = out
+        if detail is not None:
+            line, detail_all = compose_line(out, detail)
+            path = write_detail(detail_all)
+            if path:
+                line["detail_file"] = os.path.relpath(path, ROOT)
+        os.write(real_stdout, (json.dumps(line) + "\n").encode())
+    if use_dist:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
 def c4_only_main(args):
     """`--c4-only`: the C4 job alone, one JSON object on stdout (rank 0)."""
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -604,7 +675,7 @@ def main():
 
         dist.init_process_group("nccl", device_id=dev, timeout=datetime.timedelta(minutes=30))
     # host-side barrier for the wait on the separate C4 job (an RCCL barrier would keep a spinning kernel on every waiting GPU)
-    host_group = dist.new_group(backend="gloo") if (use_dist and world > 1) else None
+    host_group = dist.new_group(backend="gloo") if (use_dist and world > 1 and args.full) else None
 
     import torch_cfd_amd as tc
     from torch_cfd_amd.distributed import shard_batch
@@ -630,14 +701,14 @@ def main():
                                              for i in range(0, len(seeds), 8)]))
 
     def advance(w, k):
+        """k steps; (state, dw/dt of the last call): the two arrays forward(w, dt) hands its caller."""
         if k <= 0:
-            return w
+            return w, None
         if args.fused_steps:
-            out, _ = op(w, dt, steps=k)
-            return out
+            return op(w, dt, steps=k)
         for _ in range(k):
-            w, _ = op(w, dt)
-        return w
+            w, dwdt = op(w, dt)
+        return w, dwdt
 
     def fence():
         torch.cuda.synchronize(dev)
@@ -646,14 +717,15 @@ def main():
             torch.cuda.synchronize(dev)
 
     def timed(w, warmup, steps):
-        """W untimed warm-up steps, then exactly K steps between two fences; (state, this rank's seconds)."""
+        """W untimed warm-up steps, then exactly K steps between two fences; (state, dw/dt of the last step, this rank's
+        seconds)."""
         with torch.no_grad():
-            w = advance(w, warmup)
+            w, _ = advance(w, warmup)
             fence()
             t0 = time.perf_counter()
-            w = advance(w, steps)
+            w, dwdt = advance(w, steps)
             fence()
-            return w, time.perf_counter() - t0
+            return w, dwdt, time.perf_counter() - t0
 
     def over_ranks(elapsed):
         """(max over ranks, [per-rank seconds])."""
@@ -685,14 +757,76 @@ def main():
     # It is separate because a chunked step is ~176 short launches and an event pair per launch costs ~7 us of host
     # time and in-order queue barriers each (measured: 7.56 -> 8.78 ms per step) -- bracketing the timed regions
     # themselves would slow down the very number they produce.  `instrumented_ms_per_step` shows the difference.
+    # A plain run is one region without preheat (the defaults of `--regions` / `--preheat` without `--full`).
     with torch.no_grad():
-        w = advance(w, args.preheat)
+        w, _ = advance(w, args.preheat)
     regions = []
     for _ in range(max(1, args.regions)):
-        w, el_local = timed(w, args.warmup, args.steps)
+        w, dwdt, el_local = timed(w, args.warmup, args.steps)
         regions.append(over_ranks(el_local))
     order = sorted(range(len(regions)), key=lambda i: regions[i][0])
     elapsed, per_rank = regions[order[(len(order) - 1) // 2]]      # median (the lower one of an even count)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {"w": w, "dwdt": dwdt})
+    del dwdt
+
+    # weak: every rank advanced its own batch -> aggregate batch steps/s; strong: the ranks advanced ONE batch together
+    steps_per_s = (world if args.scaling == "weak" else 1) * args.steps / elapsed
+    S_job = (world * S) if args.scaling == "weak" else args.batch * n * m * csize   # bytes of one field set, whole job
+    # where a chunk's bytes come from: one chunk's working set (7 workspace fields per batch element) against the
+    # 256 MB Infinity Cache -- resident means the per-kernel rates below are L2 <-> Infinity-Cache rates, not DRAM rates
+    cf, cb, csrc = ctypes.c_long(0), ctypes.c_size_t(0), ctypes.c_int(0)
+    tc._lib.check(lib.tcfd_ns2d_plan_chunking(plan.handle, B, ctypes.byref(cf), ctypes.byref(cb), ctypes.byref(csrc)), "plan_chunking")
+    chunking = {"fields_per_chunk": cf.value, "chunks": (-(-B // cf.value) if cf.value else 0), "cache_bytes": cb.value,
+                "cache_source": {0: "built-in default", 1: "KFD topology of the device", 2: "TCFD_CACHE_MB"}[csrc.value]}
+    resident = 0 < cf.value < B
+    # DRAM-level estimate for the chunked step (no counter separates Infinity-Cache hits from DRAM): per forward(w, dt)
+    # call every chunk reads its slice of w once and writes w_new and dw/dt once; everything else stays on die
+    dram_est = (3.0 if resident else 73.0) * S_job
+    per_region = [round(e / args.steps * 1e3, 4) for e, _ in regions]
+    value_is = (f"median of {len(regions)} regions of W untimed + K timed steps, each between barrier + synchronize, max over ranks"
+                if len(regions) > 1 else "one region of W untimed + K timed steps between barrier + synchronize, max over ranks")
+    out = {
+        "metric": baseline_metric(),
+        "value": round(steps_per_s, 3),
+        "unit": (f"steps/s (one step = all {args.batch} fields of a GPU's batch advance one RK4-CN step)" if args.scaling == "weak"
+                 else f"steps/s (one step = the {args.batch} fields of the ONE batch, cut across the GPUs, advance one RK4-CN step)"),
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": args.scaling,
+        "vs_baseline": None,
+        "dtype": "f64" if real == torch.float64 else "f32",
+        "data": "synthetic (McWilliams random vorticity, one seed per field, generated on device)",
+        "config": {"workload": f"Kolmogorov-forced 2D turbulence, {n}^2 grid, batch {args.batch}{'/GPU' if args.scaling == 'weak' else ' in total'}, "
+                               f"RK4-CN pseudo-spectral, nu=1e-3 drag=0.1 sin(4y) forcing dt={dt:.4e}",
+                   "n": n, "batch_per_gpu": B if args.scaling == "weak" else None, "batch_total": world * B if args.scaling == "weak" else args.batch,
+                   "api": "forward(w,dt,steps=K)" if args.fused_steps else "K x forward(w,dt)",
+                   "parallelism": f"batch-sharded x{world}, no data-path collective"},
+        "timing": {"value_is": value_is, "regions_ms_per_step": per_region, "preheat_steps": args.preheat,
+                   "spread": round((max(per_region) - min(per_region)) / min(per_region), 4)},
+        "launch": {"spawned_by_bench": os.environ.get("BENCH_SPAWNED") == "1", "process_group": bool(use_dist),
+                   "rccl_world_size": dist.get_world_size() if use_dist else None,
+                   "rccl_version": ".".join(str(v) for v in torch.cuda.nccl.version()) if use_dist else None},
+        "per_rank_steps_per_s": [round(args.steps / e, 3) for e in per_rank],
+        "sample_steps_per_s": round(args.steps / elapsed * (world * B if args.scaling == "weak" else args.batch), 1),
+        "step_algo_GBps": round(70.0 * S_job * args.steps / elapsed / 1e9, 1),
+        "step_algo_frac_of_peak": round(70.0 * S_job * args.steps / elapsed / 1e9 / (HBM_PEAK_GBS * world), 4),
+        "dram_bytes_per_step_est": dram_est,
+        "dram_GBps_est": round(dram_est * args.steps / elapsed / 1e9, 1),
+        "chunking": chunking,
+    }
+    if dumped is not None:
+        out["outputs"] = dumped
+    if not args.full:
+        # the plain run ends here: nothing else is measured (--full measures the rest)
+        if rank == 0:
+            out.update(roofline=None, cpu_baseline=None, full=False)
+        return emit(out, None, rank, real_stdout, use_dist, dist)
+
     cnt = ctypes.c_int(0)
     max_rec = args.steps * 16 * 64 + 64   # every launch of every chunk of every step (<= 64 chunks)
     kinds = (ctypes.c_int * max_rec)()
@@ -702,7 +836,7 @@ def main():
         with torch.no_grad():
             tc._lib.check(lib.tcfd_ns2d_profile_begin(plan.handle, max_rec), "profile_begin")
             t1 = time.perf_counter()
-            w = advance(w, args.steps)
+            w, _ = advance(w, args.steps)
             torch.cuda.synchronize(dev)
             elapsed_instr = time.perf_counter() - t1
             tc._lib.check(lib.tcfd_ns2d_profile_end(plan.handle, max_rec, ctypes.byref(cnt), kinds, ms), "profile_end")
@@ -729,7 +863,7 @@ def main():
     if args.scaling == "weak":
         del w
         ws = initial_state(strong_seeds)
-        ws, el_s = timed(ws, args.warmup, args.steps)
+        ws, _, el_s = timed(ws, args.warmup, args.steps)
         el_s_max, el_s_all = over_ranks(el_s)
         del ws
         strong = {"value": round(args.steps / el_s_max, 3), "unit": f"steps/s of ONE batch of {args.batch} fields cut across the GPUs",
@@ -754,7 +888,7 @@ def main():
                 wp = initial_state(list(range(args.batch // N)))
                 best = None
                 for _ in range(3):      # best of three K-step regions: a region at N = 8 is only ~25 ms long
-                    wp, el_p = timed(wp, args.warmup, args.steps)
+                    wp, _, el_p = timed(wp, args.warmup, args.steps)
                     best = el_p if best is None else min(best, el_p)
                 per_n[N] = best / args.steps * 1e3
                 del wp
@@ -814,13 +948,6 @@ def main():
         tj = json.load(open(tpath))
     except Exception:
         tj = {}
-    # where a chunk's bytes come from: one chunk's working set (7 workspace fields per batch element) against the
-    # 256 MB Infinity Cache -- resident means the per-kernel rates below are L2 <-> Infinity-Cache rates, not DRAM rates
-    cf, cb, csrc = ctypes.c_long(0), ctypes.c_size_t(0), ctypes.c_int(0)
-    tc._lib.check(lib.tcfd_ns2d_plan_chunking(plan.handle, B, ctypes.byref(cf), ctypes.byref(cb), ctypes.byref(csrc)), "plan_chunking")
-    chunking = {"fields_per_chunk": cf.value, "chunks": (-(-B // cf.value) if cf.value else 0), "cache_bytes": cb.value,
-                "cache_source": {0: "built-in default", 1: "KFD topology of the device", 2: "TCFD_CACHE_MB"}[csrc.value]}
-    resident = 0 < cf.value < B
 
     def roofline_of(k):
         avg_ms = sum(per_kind[k]) / len(per_kind[k]) * nchunks
@@ -853,45 +980,7 @@ def main():
                     key=lambda k: KIND_ALGO_S[k] / (sum(per_kind[k]) / len(per_kind[k])))
         roof, roof_worst = roofline_of(dom), roofline_of(worst)
 
-    # weak: every rank advanced its own batch -> aggregate batch steps/s; strong: the ranks advanced ONE batch together
-    steps_per_s = (world if args.scaling == "weak" else 1) * args.steps / elapsed
-    S_job = (world * S) if args.scaling == "weak" else args.batch * n * m * csize   # bytes of one field set, whole job
-    # DRAM-level estimate for the chunked step (no counter separates Infinity-Cache hits from DRAM): per forward(w, dt)
-    # call every chunk reads its slice of w once and writes w_new and dw/dt once; everything else stays on die
-    dram_est = (3.0 if resident else 73.0) * S_job
-    per_region = [round(e / args.steps * 1e3, 4) for e, _ in regions]
-    out = {
-        "metric": baseline_metric(),
-        "value": round(steps_per_s, 3),
-        "unit": (f"steps/s (one step = all {args.batch} fields of a GPU's batch advance one RK4-CN step)" if args.scaling == "weak"
-                 else f"steps/s (one step = the {args.batch} fields of the ONE batch, cut across the GPUs, advance one RK4-CN step)"),
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": args.scaling,
-        "vs_baseline": None,
-        "dtype": "f64" if real == torch.float64 else "f32",
-        "data": "synthetic (McWilliams random vorticity, one seed per field, generated on device)",
-        "config": {"workload": f"Kolmogorov-forced 2D turbulence, {n}^2 grid, batch {args.batch}{'/GPU' if args.scaling == 'weak' else ' in total'}, "
-                               f"RK4-CN pseudo-spectral, nu=1e-3 drag=0.1 sin(4y) forcing dt={dt:.4e}",
-                   "n": n, "batch_per_gpu": B if args.scaling == "weak" else None, "batch_total": world * B if args.scaling == "weak" else args.batch,
-                   "api": "forward(w,dt,steps=K)" if args.fused_steps else "K x forward(w,dt)",
-                   "parallelism": f"batch-sharded x{world}, no data-path collective"},
-        "timing": {"value_is": f"median of {len(regions)} regions of W untimed + K timed steps, each between barrier + synchronize, max over ranks",
-                   "regions_ms_per_step": per_region, "preheat_steps": args.preheat,
-                   "spread": round((max(per_region) - min(per_region)) / min(per_region), 4)},
-        "launch": {"spawned_by_bench": os.environ.get("BENCH_SPAWNED") == "1", "process_group": bool(use_dist),
-                   "rccl_world_size": dist.get_world_size() if use_dist else None,
-                   "rccl_version": ".".join(str(v) for v in torch.cuda.nccl.version()) if use_dist else None},
-        "per_rank_steps_per_s": [round(args.steps / e, 3) for e in per_rank],
-        "sample_steps_per_s": round(args.steps / elapsed * (world * B if args.scaling == "weak" else args.batch), 1),
-        "step_algo_GBps": round(70.0 * S_job * args.steps / elapsed / 1e9, 1),
-        "step_algo_frac_of_peak": round(70.0 * S_job * args.steps / elapsed / 1e9 / (HBM_PEAK_GBS * world), 4),
-        "dram_bytes_per_step_est": dram_est,
-        "dram_GBps_est": round(dram_est * args.steps / elapsed / 1e9, 1),
-        "chunking": chunking,
+    out.update({
         "roofline": roof,
         "roofline_worst": roof_worst,
         "kernels": kern,
@@ -900,7 +989,8 @@ def main():
         "strong_scaling": strong,
         "strong_scaling_proxy": proxy,
         "hbm_probe": probe,
-    }
+        "full": True,
+    })
     detail = {"roofline_notes": roofline_notes,
               "dram_note": ("physical DRAM traffic of a chunked forward(w, dt) call: read w, write w_new and dw/dt (3 S); the other 70 S "
                             "of the pass model are served by the Infinity Cache" if resident else
@@ -949,15 +1039,7 @@ def main():
         torch.cuda.empty_cache()
         detail["secondary"] = secondary_job(args.secondary_timeout, with_cpu=not args.no_cpu_baseline,
                                             only=os.environ.get("BENCH_SECONDARY_ONLY", ""))     # (the env switch: a quick subset, for the tests)
-    if rank == 0:
-        line, detail_all = compose_line(out, detail)
-        path = write_detail(detail_all)
-        if path:
-            line["detail_file"] = os.path.relpath(path, ROOT)
-        os.write(real_stdout, (json.dumps(line) + "\n").encode())
-    if use_dist:
-        dist.barrier()
-        dist.destroy_process_group()
+    return emit(out, detail, rank, real_stdout, use_dist, dist)
 
 
 if __name__ == "__main__":

@@ -78,3 +78,41 @@ def test_nothing_in_bench_writes_braces_after_the_line():
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert "bench summary" not in src.replace('bench summary: {"noise"', "")
     assert src.count("os.write(real_stdout") == 3      # the host-only line, the --c4-only object, the line
+
+
+def test_plain_run_times_only_its_steps_and_full_keeps_the_regions():
+    """Without --full a run is one region of W + K steps (no preheat); --full keeps the median of five after twenty."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    plain = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert (plain.full, plain.steps, plain.warmup, plain.regions, plain.preheat, plain.dump_outputs) == (False, 7, 3, 1, 0, None)
+    full = bench.parse(["--full", "--steps", "7"])
+    assert (full.full, full.regions, full.preheat) == (True, 5, 20)
+    assert bench.parse(["--full", "--regions", "3", "--preheat", "2"]).regions == 3
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
+def test_dump_outputs_writes_the_arrays_or_a_fixed_sample(tmp_path):
+    """--dump-outputs: real / imaginary parts in the run's precision; a large output as the same seeded sample every time, at
+    most 64 MB for the two outputs of the headline workload."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    small = torch.randn(3, 16, 9, dtype=torch.complex128)
+    big = torch.randn(16, 512, 257, dtype=torch.complex64)      # 2.1 M entries: a sample of one in two
+    rec = bench.dump_outputs(str(tmp_path / "a"), {"w": small, "dwdt": big})
+    w = np.load(tmp_path / "a" / "w.npy")
+    assert w.dtype == np.float64 and np.array_equal(w[:, 0] + 1j * w[:, 1], small.numpy().reshape(-1))
+    d = np.load(tmp_path / "a" / "dwdt.npy")
+    assert d.dtype == np.float32 and d.shape == (bench.DUMP_SAMPLE, 2) and rec["shapes"]["dwdt"] == [bench.DUMP_SAMPLE, 2]
+    pairs = torch.view_as_real(big).reshape(-1, 2).numpy()[: 2 * bench.DUMP_SAMPLE].reshape(bench.DUMP_SAMPLE, 2, 2)
+    first = (d == pairs[:, 0]).all(1)
+    assert (first | (d == pairs[:, 1]).all(1)).all() and 0.4 < first.mean() < 0.6      # entry i from stratum i, spread
+    bench.dump_outputs(str(tmp_path / "b"), {"dwdt": big})
+    assert np.array_equal(d, np.load(tmp_path / "b" / "dwdt.npy"))
+    assert 2 * bench.DUMP_SAMPLE * 2 * 8 <= 64e6       # two fp64 outputs of the 64 x 1024^2 headline

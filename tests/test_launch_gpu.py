@@ -39,7 +39,7 @@ def _torchrun(script_args, extra_env=None, timeout=600):
 
 
 def test_bench_under_torchrun_with_rccl():
-    out = _torchrun(["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-sfno", "--no-cpu-baseline",
+    out = _torchrun(["bench.py", "--full", "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-sfno", "--no-cpu-baseline",
                      "--no-probe", "--no-c4"], {"BENCH_FORCE_DIST": "1"})
     assert out["n_gpus"] == 1 and out["steps"] == 3 and out["value"] > 10 and out["scaling"] == "weak"
     assert out["roofline"]["bound"].startswith("hbm") and 0 < out["roofline"]["frac"] < 1
@@ -53,8 +53,8 @@ def test_bench_strong_scaling_through_its_own_spawner():
     """`python bench.py --gpus 1 --scaling strong` with no launcher environment: the code path `--gpus 8` takes (the
     spawner only starts children for N > 1; N = 1 runs in place), headline = ONE batch cut across the ranks."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--scaling", "strong", "--steps", "3", "--warmup", "1", "--no-sfno",
-                        "--no-cpu-baseline", "--no-probe", "--no-c4"], cwd=ROOT, env=env, stdout=subprocess.PIPE,
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "1", "--scaling", "strong", "--steps", "3", "--warmup", "1",
+                        "--no-sfno", "--no-cpu-baseline", "--no-probe", "--no-c4"], cwd=ROOT, env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
@@ -69,16 +69,16 @@ def test_bench_c4_job_as_a_separate_process_tree():
     spawner) with a time limit and reads its JSON -- exercised here with one rank (BENCH_C4_SEPARATE=1)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env["BENCH_C4_SEPARATE"] = "1"
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--no-sfno", "--no-cpu-baseline", "--no-probe",
-                        "--c4-samples", "8", "--batch", "4"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--no-sfno", "--no-cpu-baseline",
+                        "--no-probe", "--c4-samples", "8", "--batch", "4"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
     assert len(lines) == 1
     c4 = json.loads(lines[0])["c4_ensemble"]
     assert "error" not in c4 and c4["finite"] is True and c4["seconds"] > 0
     # and a job that cannot finish in time is stopped, the bench line survives
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--no-sfno", "--no-cpu-baseline", "--no-probe",
-                        "--c4-samples", "64", "--batch", "4", "--c4-timeout", "0.5"], cwd=ROOT, env=env, stdout=subprocess.PIPE,
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--no-sfno", "--no-cpu-baseline",
+                        "--no-probe", "--c4-samples", "64", "--batch", "4", "--c4-timeout", "0.5"], cwd=ROOT, env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     out = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][0])
@@ -93,7 +93,8 @@ def test_bench_secondary_workloads_are_a_job_of_their_own():
 
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env["BENCH_SECONDARY_ONLY"] = "notebook"
-    cmd = [sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--regions", "3", "--no-cpu-baseline", "--no-probe", "--no-c4", "--batch", "8"]
+    cmd = [sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--regions", "3", "--no-cpu-baseline", "--no-probe",
+           "--no-c4", "--batch", "8"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     out = read_like_the_driver(r.stdout.decode(), r.stderr.decode())
@@ -110,14 +111,50 @@ def test_bench_secondary_workloads_are_a_job_of_their_own():
 def test_bench_c4_ensemble_line_small():
     """The C4 job line on one GPU with 16 samples: phases split out, dataset finite, hand-over through the pitched copies."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--no-sfno", "--no-cpu-baseline", "--no-probe",
-                        "--c4-samples", "16", "--batch", "8"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--no-sfno", "--no-cpu-baseline",
+                        "--no-probe", "--c4-samples", "16", "--batch", "8"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     out = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][0])
     c4 = out["c4_ensemble"]
     assert "error" not in c4 and c4["finite"] is True and c4["seconds"] > 0
     assert c4["stepping_s"] > 0 and c4["handover_tail_s"] >= 0 and c4["dataset_GB"] == pytest.approx(16 * 10 * 4 * 256 * 256 * 4 / 1e9, rel=0.01)
+
+
+def test_plain_bench_run_is_the_headline_and_its_outputs(tmp_path):
+    """A run without --full: W + exactly K steps, the contract's keys, none of the --full measurements; --dump-outputs writes
+    the last step's state and dw/dt in the run's precision, the same values run after run, a fixed sample of a large output."""
+    import numpy as np
+
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+
+    def run(*args):
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1"] + list(args), cwd=ROOT, env=env, stdout=subprocess.PIPE,
+                           stderr=subprocess.PIPE, timeout=600)
+        assert r.returncode == 0, r.stderr.decode()[-3000:]
+        lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip()]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+
+    outs = []
+    for i in range(2):
+        out = run("--steps", "4", "--warmup", "2", "--batch", "8", "--dump-outputs", str(tmp_path / f"d{i}"))
+        assert out["steps"] == 4 and out["warmup"] == 2 and out["value"] > 10 and out["dtype"] == "f64" and out["full"] is False
+        assert out["ms_per_step"] == pytest.approx(1e3 / out["value"], rel=1e-2) and out["higher_is_better"] is True
+        assert out["metric"] and out["unit"].startswith("steps/s") and len(out["timing"]["regions_ms_per_step"]) == 1
+        assert out["roofline"] is None and out["cpu_baseline"] is None
+        for key in ("kernels", "strong_scaling", "strong_scaling_proxy", "hbm_probe", "c4_ensemble", "fused_steps_api",
+                    "detail_file"):
+            assert key not in out, key
+        outs.append({name: np.load(tmp_path / f"d{i}" / f"{name}.npy") for name in ("w", "dwdt")})
+    for name in ("w", "dwdt"):
+        a, b = outs[0][name], outs[1][name]
+        assert a.dtype == np.float64 and a.shape == (2 ** 20, 2) and np.isfinite(a).all() and np.abs(a).max() > 0
+        assert np.array_equal(a, b), name
+    out = run("--steps", "2", "--warmup", "1", "--n", "64", "--batch", "4", "--dtype", "f32", "--dump-outputs", str(tmp_path / "s"))
+    w = np.load(tmp_path / "s" / "w.npy")
+    assert out["dtype"] == "f32" and w.dtype == np.float32 and w.shape == (4 * 64 * 33, 2)
+    assert out["outputs"]["shapes"]["w"] == [4 * 64 * 33, 2]
 
 
 def test_record_handover_page_locks_every_region_once():
