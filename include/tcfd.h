@@ -54,8 +54,9 @@ typedef enum { TCFD_C64 = 0, TCFD_C128 = 1 } tcfd_dtype;
 
 typedef struct tcfd_ns2d_plan tcfd_ns2d_plan;
 typedef struct tcfd_fno_plan tcfd_fno_plan;
+typedef struct tcfd_fvm_plan tcfd_fvm_plan;
 
-#define TCFD_ABI_VERSION 7   /* what tcfd_version() of a library built from THIS header returns */
+#define TCFD_ABI_VERSION 8   /* what tcfd_version() of a library built from THIS header returns */
 
 #ifndef TCFD_H_TYPES_ONLY   /* (the library's second compilation unit wants the types without the prototypes) */
 
@@ -485,6 +486,33 @@ int tcfd_copy_rows_to_host(void* dst_host, size_t dst_pitch, const void* src_dev
  * memory alive until it has been unregistered. */
 int tcfd_host_register(void* ptr, size_t bytes);
 int tcfd_host_unregister(void* ptr);
+
+/* ---- finite-volume (staggered MAC grid) Navier-Stokes: explicit RK stages + pressure projection ------------------
+ * Replaces NavierStokes2DFVMProjection / RKStepper of torch_cfd/fvm.py:196-431 with pressure.PressureProjection
+ * (rfft implementation).  Periodic square n x n grid (the sizes the spectral plan supports), cell size h.
+ * Fields: ux, uy (batch, n, n) real of the plan's precision (TCFD_C128: double, TCFD_C64: float); ux[b][i][j] sits
+ * at the x-face (i + 1, j + 1/2), uy at the y-face (i + 1/2, j + 1).
+ * Plan inputs (host doubles, converted on upload):
+ *   inverse_eig[2 * n * (n/2 + 1)]  complex pseudo-inverse of the summed FD-Laplacian eigenvalues (pressure.py:296-360)
+ *   force_x, force_y[n * n]          forcing / density at the staggered positions, or both NULL
+ * explicit_terms: k = convect (van Leer) + nu_over_density * laplacian + force - drag * u (fvm.py:397-409); dt enters
+ *   only through the Courant number of the limiter.
+ * project: u - grad(pinv(L) div u) (backward-difference divergence, forward-difference gradient).  ux_out may alias ux.
+ * step: `steps` RK steps of `nstages` (1..4) stages.  a[nstages * nstages] (row i = stage i, strictly lower) and
+ *   b[nstages] are the WEIGHTS of the stage increments as the caller applies them (dt * a_ij and dt * b_j, rounded as
+ *   the caller wants); a zero weight skips the term.  Stage i > 0 and the result are projected.  ux_out may alias ux_in.
+ * Workspace: tcfd_fvm_workspace_bytes(plan, batch), caller owned (project needs a prefix of it). */
+int tcfd_fvm_plan_create(tcfd_fvm_plan** plan, int n, int dtype, double h, double nu_over_density, double drag,
+                         const double* inverse_eig, const double* force_x, const double* force_y);
+void tcfd_fvm_plan_destroy(tcfd_fvm_plan* plan);
+size_t tcfd_fvm_workspace_bytes(const tcfd_fvm_plan* plan, long batch);
+int tcfd_fvm_explicit_terms(const tcfd_fvm_plan* plan, const void* ux, const void* uy, void* kx_out, void* ky_out, long batch,
+                            double dt, void* stream);
+int tcfd_fvm_project(const tcfd_fvm_plan* plan, const void* ux, const void* uy, void* ux_out, void* uy_out, long batch,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int tcfd_fvm_step(const tcfd_fvm_plan* plan, const void* ux_in, const void* uy_in, void* ux_out, void* uy_out, long batch,
+                  int steps, int nstages, const double* a, const double* b, double dt, void* workspace,
+                  size_t workspace_bytes, void* stream);
 
 #endif /* TCFD_H_TYPES_ONLY */
 

@@ -24,10 +24,10 @@ CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_NAME = "libtcfd_hip.so"
 LIB_PATH = os.path.join(CSRC, LIB_NAME)
-SOURCES = ("tcfd_ns2d.hip", "tcfd_fno.hip", "tcfd_fno_pw.hip", "tcfd_fno_tiles.hip", "tcfd_loss.hip")
+SOURCES = ("tcfd_ns2d.hip", "tcfd_fno.hip", "tcfd_fno_pw.hip", "tcfd_fno_tiles.hip", "tcfd_loss.hip", "tcfd_fvm.hip")
 
 TCFD_C64, TCFD_C128 = 0, 1
-ABI_VERSION = 7   # TCFD_ABI_VERSION of include/tcfd.h the SIGNATURES table below was written against
+ABI_VERSION = 8   # TCFD_ABI_VERSION of include/tcfd.h the SIGNATURES table below was written against
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -70,13 +70,16 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
 
 # compile jobs: (source, extra flags, object).  tcfd_ns2d.hip is compiled twice -- unit 0 = C ABI + float64 kernels, unit 1 =
 # float32 kernels -- and the FNO kernels are three files (transforms + contraction / pointwise block / tiled backward), so that
-# the hipcc processes take ~3.5 minutes side by side instead of 7 + 5 one after the other.
+# the hipcc processes take ~3.5 minutes side by side instead of 7 + 5 one after the other.  tcfd_fvm.hip (finite-volume solver) is
+# compiled twice the same way: unit 0 = C ABI + float64 kernels, unit 1 = float32 kernels.
 JOBS = (("tcfd_ns2d.hip", ("-DTCFD_UNIT=0",), "tcfd_ns2d.o"),
         ("tcfd_ns2d.hip", ("-DTCFD_UNIT=1",), "tcfd_ns2d_f32.o"),
         ("tcfd_fno.hip", (), "tcfd_fno.o"),
         ("tcfd_fno_pw.hip", (), "tcfd_fno_pw.o"),
         ("tcfd_fno_tiles.hip", (), "tcfd_fno_tiles.o"),
-        ("tcfd_loss.hip", (), "tcfd_loss.o"))
+        ("tcfd_loss.hip", (), "tcfd_loss.o"),
+        ("tcfd_fvm.hip", ("-DTCFD_UNIT=0",), "tcfd_fvm.o"),
+        ("tcfd_fvm.hip", ("-DTCFD_UNIT=1",), "tcfd_fvm_f32.o"))
 
 
 def _build_locked(srcs, verbose):
@@ -186,6 +189,12 @@ SIGNATURES = {
     "tcfd_copy_rows_to_host": (_i, [_vp, _sz, _vp, _sz, _sz, _sz, _vp]),
     "tcfd_host_register": (_i, [_vp, _sz]),
     "tcfd_host_unregister": (_i, [_vp]),
+    "tcfd_fvm_plan_create": (_i, [ctypes.POINTER(_vp), _i, _i, _d, _d, _d, _dp, _dp, _dp]),
+    "tcfd_fvm_plan_destroy": (None, [_vp]),
+    "tcfd_fvm_workspace_bytes": (_sz, [_vp, _l]),
+    "tcfd_fvm_explicit_terms": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _d, _vp]),
+    "tcfd_fvm_project": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _vp, _sz, _vp]),
+    "tcfd_fvm_step": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _i, _i, _dp, _dp, _d, _vp, _sz, _vp]),
 }
 
 

@@ -1,0 +1,536 @@
+// tcfd_fvm.hip -- MI355X (gfx950) kernels + C ABI of the finite-volume (staggered MAC grid) Navier-Stokes solver:
+// explicit Runge-Kutta stages with a pressure projection after each (reference: torch_cfd/fvm.py
+// NavierStokes2DFVMProjection :334 / RKStepper :196, pressure.py PressureProjection :68 / Pseudoinverse :153).
+//
+// Data layout: ux[b][i][j] sits at the x-face (i + 1, j + 1/2) of cell (i, j), uy[b][i][j] at the y-face (i + 1/2, j + 1);
+// q (pressure increment) and the divergence at the cell centres.  Periodic in both axes, square n x n.
+//
+// Launch sequence of one RK stage i (TCFD_UNIT 0 = fp64, 1 = fp32 instantiations):
+//   k_fvm_apply    u_i = u*_i - grad q_i (forward differences of q; skipped for stage 0, whose state is u0)
+//   k_fvm_stage    k_i = explicit_terms(u_i) in registers; u*_m (+)= c_mi k_i for every later stage m and the final sum
+//   k_fvm_div      backward-difference divergence of the next u*
+//   tcfd_rfft2 -> k_fvm_mul (x inverse eigenvalues) -> tcfd_irfft2: q of the next stage
+// The transforms are the spectral solver's kernels (tcfd_ns2d.hip) on a table-free plan held by the FVM plan.
+//
+// Every arithmetic expression restates the reference's operation order; floating-point contraction is off in this file
+// so that a * b + c rounds twice as the reference's tensor ops do.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "../../include/tcfd.h"
+
+#pragma clang fp contract(off)
+
+int tcfd_set_error(int code, const char* fmt, ...);  // defined in tcfd_ns2d.hip
+#define FAIL(...) tcfd_set_error(__VA_ARGS__)
+#define HIP_TRY(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess) return FAIL(TCFD_EHIP, "%s: %s", #expr, hipGetErrorString(e_));      \
+    } while (0)
+
+namespace {
+
+// per-point scalars, converted to the field type once (the reference multiplies fp32 tensors by Python floats, which
+// torch rounds to fp32 first)
+template <typename T>
+struct StageConst {
+    T cfl;       // dt / h                (Courant number = cfl * u)
+    T inv_h2;    // 1 / h**2              (laplacian scale per axis)
+    T sum_s;     // 1 / h**2 + 1 / h**2   (sum(scales))
+    T nu;        // viscosity / density
+    T neg_drag;  // -drag
+    T h;
+    int drag_on;
+};
+
+constexpr int MAXT = 4;   // stages of an explicit tableau (and so RK targets of one stage: the later stages + the final sum)
+
+template <typename T>
+struct Targets {
+    T* x[MAXT];
+    T* y[MAXT];
+    T c[MAXT];
+    int mode[MAXT];   // 1: P = u0 + c k,  2: P = P + c k,  3: P = u0
+    int count;
+};
+
+__device__ __forceinline__ int wrap(int i, int n) { return i < 0 ? i + n : (i >= n ? i - n : i); }
+
+// flux of the transported component c across the upper face of its control volume along one axis:
+// apply_tvd_limiter(lax_wendroff, van_leer_limiter) of c interpolated with face velocity w, times w
+// (interpolation.py:171 upwind, :246 lax_wendroff, :240 safe_div, :246 van_leer_limiter, :251 tvd; fvm.py:40 c * u)
+template <typename T>
+__device__ __forceinline__ T tvd_flux(T cm, T c0, T c1, T c2, T w, T cfl) {
+    const bool pos = w > T(0);
+    const T clow = pos ? c0 : c1;
+    const T cr = cfl * w;
+    const T d = c1 - c0;
+    const T hp = c0 + (T(0.5) * (T(1) - cr)) * d;
+    const T hn = c1 - (T(0.5) * (T(1) + cr)) * d;
+    const T chigh = pos ? hp : hn;
+    const T dd = d != T(0) ? d : T(1);
+    const T r = pos ? (c0 - cm) / dd : (c2 - c1) / dd;
+    const T rp1 = T(1) + r;
+    const T phi = r > T(0) ? (T(2) * r) / (rp1 != T(0) ? rp1 : T(1)) : T(0);
+    const T ci = clow - (clow - chigh) * phi;
+    return ci * w;
+}
+
+// linear interpolation to the half-way point: floor_weight * shift(0) + ceil_weight * shift(1) (interpolation.py:16)
+template <typename T>
+__device__ __forceinline__ T half(T a, T b) { return T(0.5) * a + T(0.5) * b; }
+
+// explicit_terms of both velocity components at cell (i, j) of field plane X / Y (fvm.py:397-409):
+// ((convect + nu lap) + f) + (-drag) u
+template <typename T>
+__device__ __forceinline__ void explicit_point(const T* __restrict__ X, const T* __restrict__ Y, const T* __restrict__ fx,
+                                               const T* __restrict__ fy, int i, int j, int n, const StageConst<T>& s,
+                                               T& kx, T& ky) {
+    const int im2 = wrap(i - 2, n), im1 = wrap(i - 1, n), ip1 = wrap(i + 1, n), ip2 = wrap(i + 2, n);
+    const int jm2 = wrap(j - 2, n), jm1 = wrap(j - 1, n), jp1 = wrap(j + 1, n), jp2 = wrap(j + 2, n);
+    auto at = [n](const T* p, int a, int b) { return p[(size_t)a * n + b]; };
+
+    // ---- ux: control volume centred at its own face, faces at (i + 3/2, j + 1/2) and (i + 1, j + 1)
+    const T x00 = at(X, i, j);
+    const T xm2 = at(X, im2, j), xm1 = at(X, im1, j), xp1 = at(X, ip1, j), xp2 = at(X, ip2, j);
+    const T xjm2 = at(X, i, jm2), xjm1 = at(X, i, jm1), xjp1 = at(X, i, jp1), xjp2 = at(X, i, jp2);
+    const T y00 = at(Y, i, j);
+    const T yp1 = at(Y, ip1, j), yjm1 = at(Y, i, jm1), yp1jm1 = at(Y, ip1, jm1);
+    T adv_x;
+    {
+        const T f_hi = tvd_flux(xm1, x00, xp1, xp2, half(x00, xp1), s.cfl);
+        const T f_lo = tvd_flux(xm2, xm1, x00, xp1, half(xm1, x00), s.cfl);
+        const T g_hi = tvd_flux(xjm1, x00, xjp1, xjp2, half(y00, yp1), s.cfl);
+        const T g_lo = tvd_flux(xjm2, xjm1, x00, xjp1, half(yjm1, yp1jm1), s.cfl);
+        adv_x = -((f_hi - f_lo) / s.h + (g_hi - g_lo) / s.h);
+    }
+    // ---- uy: faces at (i + 1, j + 1) and (i + 1/2, j + 3/2)
+    const T ym2 = at(Y, im2, j), ym1 = at(Y, im1, j), yp2 = at(Y, ip2, j);
+    const T yjm2 = at(Y, i, jm2), yjp1 = at(Y, i, jp1), yjp2 = at(Y, i, jp2);
+    const T xm1jp1 = at(X, im1, jp1);
+    T adv_y;
+    {
+        const T f_hi = tvd_flux(ym1, y00, yp1, yp2, half(x00, xjp1), s.cfl);
+        const T f_lo = tvd_flux(ym2, ym1, y00, yp1, half(xm1, xm1jp1), s.cfl);
+        const T g_hi = tvd_flux(yjm1, y00, yjp1, yjp2, half(y00, yjp1), s.cfl);
+        const T g_lo = tvd_flux(yjm2, yjm1, y00, yjp1, half(yjm1, y00), s.cfl);
+        adv_y = -((f_hi - f_lo) / s.h + (g_hi - g_lo) / s.h);
+    }
+    // laplacian (finite_differences.py:150): (-2 u) * sum(scales) + (u[-1] + u[+1]) * s0 + (u[-1] + u[+1]) * s1
+    T lap_x = (T(-2) * x00) * s.sum_s;
+    lap_x = lap_x + (xm1 + xp1) * s.inv_h2;
+    lap_x = lap_x + (xjm1 + xjp1) * s.inv_h2;
+    T lap_y = (T(-2) * y00) * s.sum_s;
+    lap_y = lap_y + (ym1 + yp1) * s.inv_h2;
+    lap_y = lap_y + (yjm1 + yjp1) * s.inv_h2;
+
+    kx = adv_x + s.nu * lap_x;
+    ky = adv_y + s.nu * lap_y;
+    if (fx) {
+        const size_t p = (size_t)i * n + j;
+        kx = kx + fx[p];
+        ky = ky + fy[p];
+    }
+    if (s.drag_on) {
+        kx = kx + x00 * s.neg_drag;
+        ky = ky + y00 * s.neg_drag;
+    }
+}
+
+// one thread per cell; blockIdx.z = sample
+template <typename T>
+__global__ void __launch_bounds__(256) k_fvm_stage(const T* __restrict__ ux, const T* __restrict__ uy, const T* __restrict__ u0x,
+                                                   const T* __restrict__ u0y, const T* __restrict__ fx, const T* __restrict__ fy,
+                                                   T* __restrict__ kx_out, T* __restrict__ ky_out, Targets<T> tg, StageConst<T> s,
+                                                   int n) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = blockIdx.y * blockDim.y + threadIdx.y;
+    if (i >= n || j >= n) return;
+    const size_t plane = (size_t)n * n;
+    const size_t base = (size_t)blockIdx.z * plane;
+    T kx, ky;
+    explicit_point(ux + base, uy + base, fx, fy, i, j, n, s, kx, ky);
+    const size_t p = base + (size_t)i * n + j;
+    if (kx_out) {
+        kx_out[p] = kx;
+        ky_out[p] = ky;
+    }
+    for (int t = 0; t < tg.count; ++t) {
+        const int mode = tg.mode[t];
+        const T c = tg.c[t];
+        T px, py;
+        if (mode == 2) {
+            px = tg.x[t][p];
+            py = tg.y[t][p];
+        } else {
+            px = u0x[p];
+            py = u0y[p];
+        }
+        if (mode != 3) {
+            px = px + kx * c;
+            py = py + ky * c;
+        }
+        tg.x[t][p] = px;
+        tg.y[t][p] = py;
+    }
+}
+
+// div = (ux - ux[i-1]) / h + (uy - uy[j-1]) / h  (finite_differences.py:116-135)
+template <typename T>
+__global__ void __launch_bounds__(256) k_fvm_div(const T* __restrict__ ux, const T* __restrict__ uy, T* __restrict__ div, T h, int n) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = blockIdx.y * blockDim.y + threadIdx.y;
+    if (i >= n || j >= n) return;
+    const size_t base = (size_t)blockIdx.z * n * n;
+    const size_t p = base + (size_t)i * n + j;
+    const T dx = (ux[p] - ux[base + (size_t)wrap(i - 1, n) * n + j]) / h;
+    const T dy = (uy[p] - uy[base + (size_t)i * n + wrap(j - 1, n)]) / h;
+    div[p] = dx + dy;
+}
+
+// spectrum *= inverse eigenvalues (pressure.py: multiplier * fft(value)), complex (re, im) pairs
+template <typename T>
+__global__ void __launch_bounds__(256) k_fvm_mul(T* __restrict__ spec, const T* __restrict__ inv, long plane, long total) {
+    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    const long t = e % plane;
+    const T ar = inv[2 * t], ai = inv[2 * t + 1];
+    const T br = spec[2 * e], bi = spec[2 * e + 1];
+    spec[2 * e] = ar * br - ai * bi;
+    spec[2 * e + 1] = ar * bi + ai * br;
+}
+
+// out = P - (q[+1] - q) / h per component (pressure.py:100-106 with forward_difference, finite_differences.py:69)
+template <typename T>
+__global__ void __launch_bounds__(256) k_fvm_apply(const T* __restrict__ px, const T* __restrict__ py, const T* __restrict__ q,
+                                                   T* __restrict__ ox, T* __restrict__ oy, T h, int n) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = blockIdx.y * blockDim.y + threadIdx.y;
+    if (i >= n || j >= n) return;
+    const size_t base = (size_t)blockIdx.z * n * n;
+    const size_t p = base + (size_t)i * n + j;
+    const T q0 = q[p];
+    const T gx = (q[base + (size_t)wrap(i + 1, n) * n + j] - q0) / h;
+    const T gy = (q[base + (size_t)i * n + wrap(j + 1, n)] - q0) / h;
+    ox[p] = px[p] - gx;
+    oy[p] = py[p] - gy;
+}
+
+}  // namespace
+
+#if TCFD_UNIT == 1
+using Real = float;
+#define FVM_SUFFIX f32
+#else
+using Real = double;
+#define FVM_SUFFIX f64
+#endif
+
+struct tcfd_fvm_plan {
+    int n;
+    int dtype;                 // TCFD_C128: fp64 fields, TCFD_C64: fp32
+    double h, nu, drag;
+    tcfd_ns2d_plan* fft;       // table-free spectral plan: the rfft2 / irfft2 kernels
+    void* inv;                 // (n, n/2 + 1) complex inverse eigenvalues, field precision
+    void* fx;                  // (n, n) forcing / density per component, field precision (NULL: no forcing)
+    void* fy;
+    size_t fft_ws;             // tcfd_ns2d_workspace_bytes of the transform plan, per batch, computed at call time
+};
+
+// ---- per-precision launchers (one compilation unit each); the C ABI (unit 0) dispatches on the plan's dtype
+#define CAT2(a, b) a##b
+#define CAT(a, b) CAT2(a, b)
+#define FVMFN(name) CAT(name##_, FVM_SUFFIX)
+
+static dim3 cell_grid(int n, long batch) { return dim3((unsigned)((n + 63) / 64), (unsigned)((n + 3) / 4), (unsigned)batch); }
+static const dim3 kCellBlock(64, 4, 1);
+
+static StageConst<Real> stage_const(const tcfd_fvm_plan* p, double dt) {
+    StageConst<Real> s;
+    const double inv_h2 = 1.0 / (p->h * p->h);
+    s.cfl = (Real)(dt / p->h);
+    s.inv_h2 = (Real)inv_h2;
+    s.sum_s = (Real)(inv_h2 + inv_h2);
+    s.nu = (Real)p->nu;
+    s.neg_drag = (Real)(-p->drag);
+    s.h = (Real)p->h;
+    s.drag_on = p->drag > 0.0;
+    return s;
+}
+
+int FVMFN(fvm_stage_launch)(const tcfd_fvm_plan* p, const void* ux, const void* uy, const void* u0x, const void* u0y, void* kx,
+                            void* ky, void* const* tx, void* const* ty, const double* c, const int* mode, int count, long batch,
+                            double dt, hipStream_t st) {
+    Targets<Real> tg;
+    tg.count = count;
+    for (int t = 0; t < MAXT; ++t) {
+        tg.x[t] = t < count ? (Real*)tx[t] : nullptr;
+        tg.y[t] = t < count ? (Real*)ty[t] : nullptr;
+        tg.c[t] = t < count ? (Real)c[t] : Real(0);
+        tg.mode[t] = t < count ? mode[t] : 0;
+    }
+    hipLaunchKernelGGL(k_fvm_stage<Real>, cell_grid(p->n, batch), kCellBlock, 0, st, (const Real*)ux, (const Real*)uy,
+                       (const Real*)u0x, (const Real*)u0y, (const Real*)p->fx, (const Real*)p->fy, (Real*)kx, (Real*)ky, tg,
+                       stage_const(p, dt), p->n);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int FVMFN(fvm_div_launch)(const tcfd_fvm_plan* p, const void* ux, const void* uy, void* div, long batch, hipStream_t st) {
+    hipLaunchKernelGGL(k_fvm_div<Real>, cell_grid(p->n, batch), kCellBlock, 0, st, (const Real*)ux, (const Real*)uy, (Real*)div,
+                       (Real)p->h, p->n);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int FVMFN(fvm_mul_launch)(const tcfd_fvm_plan* p, void* spec, long batch, hipStream_t st) {
+    const long plane = (long)p->n * (p->n / 2 + 1);
+    const long total = plane * batch;
+    hipLaunchKernelGGL(k_fvm_mul<Real>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (Real*)spec, (const Real*)p->inv,
+                       plane, total);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int FVMFN(fvm_apply_launch)(const tcfd_fvm_plan* p, const void* px, const void* py, const void* q, void* ox, void* oy, long batch,
+                            hipStream_t st) {
+    hipLaunchKernelGGL(k_fvm_apply<Real>, cell_grid(p->n, batch), kCellBlock, 0, st, (const Real*)px, (const Real*)py,
+                       (const Real*)q, (Real*)ox, (Real*)oy, (Real)p->h, p->n);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+#if TCFD_UNIT != 1
+// ================================================================ C ABI (unit 0)
+int fvm_stage_launch_f32(const tcfd_fvm_plan*, const void*, const void*, const void*, const void*, void*, void*, void* const*,
+                         void* const*, const double*, const int*, int, long, double, hipStream_t);
+int fvm_div_launch_f32(const tcfd_fvm_plan*, const void*, const void*, void*, long, hipStream_t);
+int fvm_mul_launch_f32(const tcfd_fvm_plan*, void*, long, hipStream_t);
+int fvm_apply_launch_f32(const tcfd_fvm_plan*, const void*, const void*, const void*, void*, void*, long, hipStream_t);
+
+namespace {
+
+bool is_f64(const tcfd_fvm_plan* p) { return p->dtype == TCFD_C128; }
+size_t real_bytes(const tcfd_fvm_plan* p) { return is_f64(p) ? 8 : 4; }
+size_t field_bytes(const tcfd_fvm_plan* p, long batch) { return (size_t)batch * p->n * p->n * real_bytes(p); }
+size_t spec_bytes(const tcfd_fvm_plan* p, long batch) { return (size_t)batch * p->n * (p->n / 2 + 1) * 2 * real_bytes(p); }
+size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
+
+int stage_launch(const tcfd_fvm_plan* p, const void* ux, const void* uy, const void* u0x, const void* u0y, void* kx, void* ky,
+                 void* const* tx, void* const* ty, const double* c, const int* mode, int count, long batch, double dt,
+                 hipStream_t st) {
+    return is_f64(p) ? fvm_stage_launch_f64(p, ux, uy, u0x, u0y, kx, ky, tx, ty, c, mode, count, batch, dt, st)
+                     : fvm_stage_launch_f32(p, ux, uy, u0x, u0y, kx, ky, tx, ty, c, mode, count, batch, dt, st);
+}
+int apply_launch(const tcfd_fvm_plan* p, const void* px, const void* py, const void* q, void* ox, void* oy, long batch,
+                 hipStream_t st) {
+    return is_f64(p) ? fvm_apply_launch_f64(p, px, py, q, ox, oy, batch, st) : fvm_apply_launch_f32(p, px, py, q, ox, oy, batch, st);
+}
+
+// workspace carve: [div | spectrum | q | transform scratch] for the projection, then the RK buffers of tcfd_fvm_step
+struct Carve {
+    void *div, *spec, *q, *fftws;
+    size_t fftws_bytes;
+    void *u0x, *u0y, *ucx, *ucy;
+    void *px[MAXT], *py[MAXT];
+    size_t total;
+};
+
+Carve carve(const tcfd_fvm_plan* p, long batch, void* ws, bool rk) {
+    Carve c{};
+    char* b = (char*)ws;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        void* r = b ? b + off : nullptr;
+        off += align_up(bytes);
+        return r;
+    };
+    const size_t F = field_bytes(p, batch);
+    c.div = take(F);
+    c.spec = take(spec_bytes(p, batch));
+    c.q = take(F);
+    c.fftws_bytes = tcfd_ns2d_workspace_bytes(p->fft, batch);
+    c.fftws = take(c.fftws_bytes);
+    if (rk) {
+        c.u0x = take(F);
+        c.u0y = take(F);
+        c.ucx = take(F);
+        c.ucy = take(F);
+        for (int t = 0; t < MAXT; ++t) {
+            c.px[t] = take(F);
+            c.py[t] = take(F);
+        }
+    }
+    c.total = off;
+    return c;
+}
+
+// q of the field (px, py) into c.q
+int solve_q(const tcfd_fvm_plan* p, const void* px, const void* py, long batch, const Carve& c, hipStream_t st) {
+    int rc = is_f64(p) ? fvm_div_launch_f64(p, px, py, c.div, batch, st) : fvm_div_launch_f32(p, px, py, c.div, batch, st);
+    if (rc) return rc;
+    if ((rc = tcfd_rfft2(p->fft, c.div, c.spec, batch, st))) return rc;
+    rc = is_f64(p) ? fvm_mul_launch_f64(p, c.spec, batch, st) : fvm_mul_launch_f32(p, c.spec, batch, st);
+    if (rc) return rc;
+    return tcfd_irfft2(p->fft, c.spec, c.q, batch, c.fftws, c.fftws_bytes, st);
+}
+
+int check_ws(const tcfd_fvm_plan* p, long batch, void* ws, size_t ws_bytes, bool rk) {
+    const size_t need = carve(p, batch, nullptr, rk).total;
+    if (!ws || ws_bytes < need) return FAIL(TCFD_EWORKSPACE, "fvm: workspace of %zu bytes, %zu needed", ws_bytes, need);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tcfd_fvm_plan_create(tcfd_fvm_plan** out, int n, int dtype, double h, double nu_over_density, double drag,
+                                      const double* inverse_eig, const double* force_x, const double* force_y) {
+    if (!out || !inverse_eig) return FAIL(TCFD_EINVAL, "fvm_plan_create: null argument");
+    *out = nullptr;
+    if (dtype != TCFD_C64 && dtype != TCFD_C128) return FAIL(TCFD_EINVAL, "fvm_plan_create: dtype %d", dtype);
+    if (!(h > 0.0)) return FAIL(TCFD_EINVAL, "fvm_plan_create: cell size %g", h);
+    if ((force_x == nullptr) != (force_y == nullptr)) return FAIL(TCFD_EINVAL, "fvm_plan_create: give both forcing components or none");
+    const int m = n / 2 + 1;
+    std::vector<double> zx(n, 0.0), zy(m, 0.0), lin((size_t)n * m, 0.0), mask((size_t)n * m, 1.0);
+    tcfd_ns2d_plan* fft = nullptr;
+    int rc = tcfd_ns2d_plan_create(&fft, n, dtype, zx.data(), zy.data(), lin.data(), mask.data(), nullptr);
+    if (rc) return rc;   // (the transform plan's message names the unsupported size)
+    tcfd_fvm_plan* p = new tcfd_fvm_plan{};
+    p->n = n;
+    p->dtype = dtype;
+    p->h = h;
+    p->nu = nu_over_density;
+    p->drag = drag;
+    p->fft = fft;
+    const bool f64 = dtype == TCFD_C128;
+    auto upload = [&](const double* src, size_t count, void** dst) -> int {
+        const size_t bytes = count * (f64 ? 8 : 4);
+        if (hipMalloc(dst, bytes) != hipSuccess) return FAIL(TCFD_ENOMEM, "fvm_plan_create: hipMalloc(%zu)", bytes);
+        hipError_t e;
+        if (f64) {
+            e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+        } else {
+            std::vector<float> tmp(count);
+            for (size_t k = 0; k < count; ++k) tmp[k] = (float)src[k];
+            e = hipMemcpy(*dst, tmp.data(), bytes, hipMemcpyHostToDevice);
+        }
+        return e == hipSuccess ? 0 : FAIL(TCFD_EHIP, "fvm_plan_create: upload: %s", hipGetErrorString(e));
+    };
+    rc = upload(inverse_eig, (size_t)2 * n * m, &p->inv);
+    if (!rc && force_x) rc = upload(force_x, (size_t)n * n, &p->fx);
+    if (!rc && force_y) rc = upload(force_y, (size_t)n * n, &p->fy);
+    if (rc) {
+        tcfd_fvm_plan_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return 0;
+}
+
+void tcfd_fvm_plan_destroy(tcfd_fvm_plan* p) {
+    if (!p) return;
+    if (p->inv) (void)hipFree(p->inv);
+    if (p->fx) (void)hipFree(p->fx);
+    if (p->fy) (void)hipFree(p->fy);
+    if (p->fft) tcfd_ns2d_plan_destroy(p->fft);
+    delete p;
+}
+
+size_t tcfd_fvm_workspace_bytes(const tcfd_fvm_plan* p, long batch) {
+    if (!p || batch <= 0) return 0;
+    return carve(p, batch, nullptr, true).total;
+}
+
+int tcfd_fvm_explicit_terms(const tcfd_fvm_plan* p, const void* ux, const void* uy, void* kx, void* ky, long batch,
+                                         double dt, void* stream) {
+    if (!p || !ux || !uy || !kx || !ky || batch <= 0) return FAIL(TCFD_EINVAL, "fvm_explicit_terms: bad argument");
+    return stage_launch(p, ux, uy, ux, uy, kx, ky, nullptr, nullptr, nullptr, nullptr, 0, batch, dt, (hipStream_t)stream);
+}
+
+int tcfd_fvm_project(const tcfd_fvm_plan* p, const void* ux, const void* uy, void* ux_out, void* uy_out, long batch,
+                                  void* ws, size_t ws_bytes, void* stream) {
+    if (!p || !ux || !uy || !ux_out || !uy_out || batch <= 0) return FAIL(TCFD_EINVAL, "fvm_project: bad argument");
+    int rc = check_ws(p, batch, ws, ws_bytes, false);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const Carve c = carve(p, batch, ws, false);
+    if ((rc = solve_q(p, ux, uy, batch, c, st))) return rc;
+    return apply_launch(p, ux, uy, c.q, ux_out, uy_out, batch, st);
+}
+
+int tcfd_fvm_step(const tcfd_fvm_plan* p, const void* ux_in, const void* uy_in, void* ux_out, void* uy_out,
+                               long batch, int steps, int nstages, const double* a, const double* b, double dt, void* ws,
+                               size_t ws_bytes, void* stream) {
+    if (!p || !ux_in || !uy_in || !ux_out || !uy_out || batch <= 0 || steps < 0 || !b || (nstages > 1 && !a))
+        return FAIL(TCFD_EINVAL, "fvm_step: bad argument");
+    if (nstages < 1 || nstages > MAXT) return FAIL(TCFD_EINVAL, "fvm_step: %d stages (1 .. %d supported)", nstages, MAXT);
+    for (int i = 0; i < nstages; ++i)
+        for (int j = i; j < nstages; ++j)
+            if (nstages > 1 && a[i * nstages + j] != 0.0)
+                return FAIL(TCFD_EINVAL, "fvm_step: a[%d][%d] != 0: only explicit (strictly lower) tableaux", i, j);
+    int rc = check_ws(p, batch, ws, ws_bytes, true);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const Carve c = carve(p, batch, ws, true);
+    const size_t F = field_bytes(p, batch);
+    if (steps == 0) {
+        if (ux_out != ux_in) HIP_TRY(hipMemcpyAsync(ux_out, ux_in, F, hipMemcpyDeviceToDevice, st));
+        if (uy_out != uy_in) HIP_TRY(hipMemcpyAsync(uy_out, uy_in, F, hipMemcpyDeviceToDevice, st));
+        return 0;
+    }
+    HIP_TRY(hipMemcpyAsync(c.u0x, ux_in, F, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c.u0y, uy_in, F, hipMemcpyDeviceToDevice, st));
+    // targets of stage j: every later stage m (buffer m - 1) and the final sum (buffer nstages - 1).  A target is
+    // initialised from u0 at the first stage whose weight on it is nonzero (or, with no nonzero weight, at the stage right
+    // before it is read), then accumulated; zero weights are skipped as the reference skips them.
+    auto weight = [&](int m, int j) { return m < nstages ? a[m * nstages + j] : b[j]; };
+    for (int s = 0; s < steps; ++s) {
+        const bool last = s == steps - 1;
+        for (int j = 0; j < nstages; ++j) {
+            void* tx[MAXT];
+            void* ty[MAXT];
+            double cw[MAXT];
+            int mode[MAXT];
+            int count = 0;
+            for (int m = j + 1; m <= nstages; ++m) {
+                const double w = weight(m, j);
+                bool started = false;
+                for (int jj = 0; jj < j; ++jj) started = started || weight(m, jj) != 0.0;
+                int md = 0;
+                if (w != 0.0) md = started ? 2 : 1;
+                else if (!started && j == m - 1) md = 3;
+                if (!md) continue;
+                tx[count] = c.px[m - 1];
+                ty[count] = c.py[m - 1];
+                cw[count] = w;
+                mode[count] = md;
+                ++count;
+            }
+            const void* sx = j == 0 ? c.u0x : c.ucx;
+            const void* sy = j == 0 ? c.u0y : c.ucy;
+            if ((rc = stage_launch(p, sx, sy, c.u0x, c.u0y, nullptr, nullptr, tx, ty, cw, mode, count, batch, dt, st))) return rc;
+            // project the next stage's state (or the final sum)
+            const int m = j + 1;
+            if ((rc = solve_q(p, c.px[m - 1], c.py[m - 1], batch, c, st))) return rc;
+            if (m < nstages) {
+                if ((rc = apply_launch(p, c.px[m - 1], c.py[m - 1], c.q, c.ucx, c.ucy, batch, st))) return rc;
+            } else {
+                void* ox = last ? ux_out : c.u0x;
+                void* oy = last ? uy_out : c.u0y;
+                if ((rc = apply_launch(p, c.px[m - 1], c.py[m - 1], c.q, ox, oy, batch, st))) return rc;
+            }
+        }
+    }
+    return 0;
+}
+
+}  // extern "C"
+#endif

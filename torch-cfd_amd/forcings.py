@@ -78,8 +78,13 @@ class ForcingFn(nn.Module):
     def velocity_eval(self, grid: Optional[Grid], velocity=None):
         grid = self.grid if grid is None else grid
         off_x, off_y = self.offsets
-        (x, _), (_, y) = grid.mesh(off_x), grid.mesh(off_y)
-        fx, fy = self.momentum(x, y)
+        # each component at its own sample positions (the reference samples fx on the mesh of offsets[0], fy on that of
+        # offsets[1], torch_cfd/forcings.py:158-178); with equal offsets this is one evaluation
+        if off_x == off_y:
+            fx, fy = self.momentum(*grid.mesh(off_x))
+        else:
+            fx, _ = self.momentum(*grid.mesh(off_x))
+            _, fy = self.momentum(*grid.mesh(off_y))
         return FieldArray(fx, off_x, grid), FieldArray(fy, off_y, grid)
 
     def vorticity_eval(self, grid: Optional[Grid], vorticity=None):

@@ -1,0 +1,383 @@
+"""Finite-volume Navier-Stokes solver on the staggered (MAC) grid: explicit Runge-Kutta stages, each followed by a pressure
+projection (torch_cfd/fvm.py ``RKStepper`` :196 and ``NavierStokes2DFVMProjection`` :334, pressure.py
+``PressureProjection`` :68 / ``Pseudoinverse`` :153).
+
+The velocity is a pair ``(ux, uy)`` of ``(n, n)`` or ``(B, n, n)`` tensors: ``ux`` at the x-faces (offset ``(1, 1/2)``),
+``uy`` at the y-faces (``(1/2, 1)``), the form ``initial_conditions.filtered_velocity_field`` returns; objects with a
+``.data`` tensor (the reference's ``GridVariableVector``) are accepted too.  Periodic square grids only -- all the
+reference implements (its ``advect_general`` raises otherwise).
+
+Every stage runs on the HIP kernels of ``csrc/tcfd_fvm.hip`` (C ABI ``tcfd_fvm_*``); the pressure solve uses the
+project's own rfft2 / irfft2 kernels.  Forward only: a tableau whose parameters require grad raises while grad mode is on.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+import weakref
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import torch
+import torch.nn as nn
+
+from . import _lib
+from .grids import Grid
+
+_FP = {torch.float64: _lib.TCFD_C128, torch.float32: _lib.TCFD_C64}
+
+
+def _tensor_of(x) -> torch.Tensor:
+    return x if isinstance(x, torch.Tensor) else x.data
+
+
+def _as_pair(u) -> Tuple[torch.Tensor, torch.Tensor]:
+    if len(u) != 2:
+        raise ValueError(f"expected a velocity pair (ux, uy), got {len(u)} components")
+    ux, uy = (_tensor_of(c) for c in u)
+    if ux.shape != uy.shape or ux.dtype != uy.dtype or ux.device != uy.device:
+        raise ValueError(f"velocity components differ: {tuple(ux.shape)} {ux.dtype} {ux.device} vs "
+                         f"{tuple(uy.shape)} {uy.dtype} {uy.device}")
+    return ux, uy
+
+
+def _check_periodic(bcs) -> None:
+    """``bcs``: None (periodic) or per-component boundary conditions with ``.types`` (the reference's classes)."""
+    if bcs is None:
+        return
+    for bc in (bcs if isinstance(bcs, (list, tuple)) else [bcs]):
+        types = getattr(bc, "types", None)
+        if types is None:
+            raise NotImplementedError(f"boundary condition {bc!r}: only periodic boundaries are implemented")
+        for pair in types:
+            for t in pair:
+                if str(t).lower() != "periodic":
+                    raise NotImplementedError(f"boundary type {t!r}: the finite-volume solver implements periodic "
+                                              "boundaries only (as the reference's advect_general)")
+
+
+def _square_step(grid: Grid) -> float:
+    if grid.ndim != 2 or grid.shape[0] != grid.shape[1] or not math.isclose(grid.step[0], grid.step[1], rel_tol=0, abs_tol=0):
+        raise NotImplementedError(f"{grid}: the finite-volume solver runs on square n x n grids with equal cell sizes")
+    return grid.step[0]
+
+
+# ----------------------------------------------------------------------------- tableau
+class RKStepper(nn.Module):
+    """Explicit Runge-Kutta tableau ``{"a": rows, "b": weights}`` (torch_cfd/fvm.py:196).
+
+    The parameters are stored as the reference stores them -- ``params.a.{i}`` (row i = stage i + 1), ``params.b`` --
+    in ``dtype``, float32 by default.  The stage weights are formed as the reference forms them, ``dt * a_ij`` in the
+    parameters' precision: an fp64 run of classic RK4 steps with ``b = float32(1/6)``, as there.  Zero entries are
+    skipped."""
+
+    _METHOD_MAP = {
+        "forward_euler": {"a": [], "b": [1.0]},
+        "midpoint": {"a": [[1 / 2]], "b": [0, 1.0]},
+        "heun_rk2": {"a": [[1.0]], "b": [1 / 2, 1 / 2]},
+        "classic_rk4": {
+            "a": [[1 / 2], [0.0, 1 / 2], [0.0, 0.0, 1.0]],
+            "b": [1 / 6, 1 / 3, 1 / 3, 1 / 6],
+        },
+    }
+    MAX_STAGES = 4
+
+    def __init__(self, tableau: Optional[Dict[str, List]] = None, method: Optional[str] = None,
+                 dtype: Optional[torch.dtype] = torch.float32, requires_grad: bool = False, **kwargs):
+        super().__init__()
+        self.dtype = dtype
+        self.requires_grad = requires_grad
+        if tableau is not None:
+            self._tableau, self._method = tableau, None
+        else:
+            if method not in self._METHOD_MAP:
+                raise ValueError(f"Unknown RK method: {method}")
+            self._tableau, self._method = self._METHOD_MAP[method], method
+        self._set_params(self._tableau)
+
+    @property
+    def method(self):
+        return self._method
+
+    @property
+    def tableau(self):
+        return self._tableau
+
+    @property
+    def num_stages(self) -> int:
+        return len(self.params["b"])
+
+    def _set_params(self, tableau: Dict[str, List]) -> None:
+        a, b = tableau["a"], tableau["b"]
+        if len(a) + 1 != len(b):
+            raise ValueError("Inconsistent Butcher tableau: len(a) + 1 != len(b)")
+        for i, row in enumerate(a):
+            if len(row) != i + 1:
+                raise ValueError(f"Inconsistent Butcher tableau: row {i} of a has {len(row)} entries, an explicit "
+                                 f"tableau has {i + 1} there")
+        if len(b) > self.MAX_STAGES:
+            raise ValueError(f"{len(b)} stages: the finite-volume kernels take explicit tableaux of up to "
+                             f"{self.MAX_STAGES} stages")
+        self.params = nn.ParameterDict()
+        self.params["a"] = nn.ParameterList()
+        for row in a:
+            self.params["a"].append(nn.Parameter(torch.tensor(row, dtype=self.dtype, requires_grad=self.requires_grad)))
+        self.params["b"] = nn.Parameter(torch.tensor(b, dtype=self.dtype, requires_grad=self.requires_grad))
+
+    @classmethod
+    def from_method(cls, method: str = "forward_euler", requires_grad: bool = False, **kwargs):
+        return cls(method=method, requires_grad=requires_grad, **kwargs)
+
+    def _check_no_grad(self) -> None:
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError("RKStepper: the finite-volume step is forward only; its tableau parameters require "
+                                      "grad. Run under torch.no_grad() or build the stepper with requires_grad=False.")
+
+    def weights(self, dt: float) -> Tuple[List[float], List[float]]:
+        """(a, b) as the kernels take them: ``a`` row-major (stages x stages, row i = stage i) and ``b``, each entry
+        ``dt * coefficient`` evaluated as the reference does (in the parameters' dtype), 0 for a skipped term."""
+        s = self.num_stages
+        a = [0.0] * (s * s)
+        with torch.no_grad():
+            alpha, beta = self.params["a"], self.params["b"]
+            for i in range(1, s):
+                for j in range(i):
+                    if alpha[i - 1][j] != 0:
+                        a[i * s + j] = float(dt * alpha[i - 1][j])
+            b = [float(dt * beta[j]) if beta[j] != 0 else 0.0 for j in range(s)]
+        return a, b
+
+    def forward(self, u0, dt: float, equation: "NavierStokes2DFVMProjection"):
+        """One step of ``equation`` (the reference's calling convention ``step_fn.forward(v, dt, equation=ns2d)``)."""
+        return equation.advance(u0, dt, steps=1, solver=self)
+
+
+# ----------------------------------------------------------------------------- device plan
+class _FvmPlan:
+    """Owns one ``tcfd_fvm_plan`` (inverse-eigenvalue and forcing tables) + a workspace."""
+
+    def __init__(self, n: int, dtype: torch.dtype, device: torch.device, h: float, nu: float, drag: float,
+                 inverse: torch.Tensor, force: Optional[Tuple[torch.Tensor, torch.Tensor]]):
+        self.lib = _lib.load()
+        self.n, self.dtype, self.device = n, dtype, torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.TcfdError("torch-cfd_amd runs on HIP devices only (no CPU fallback); got " + str(device))
+        inv = torch.view_as_real(inverse.detach().to("cpu", torch.complex128).contiguous()).contiguous()
+        assert inv.shape == (n, n // 2 + 1, 2)
+        keep = [inv]
+        fx = fy = None
+        if force is not None:
+            fx_t, fy_t = (f.detach().to("cpu", torch.float64).expand(n, n).contiguous() for f in force)
+            keep += [fx_t, fy_t]
+            fx, fy = _lib.dptr_of_tensor(fx_t), _lib.dptr_of_tensor(fy_t)
+        handle = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            rc = self.lib.tcfd_fvm_plan_create(ctypes.byref(handle), n, _FP[dtype], float(h), float(nu), float(drag),
+                                               _lib.dptr_of_tensor(inv), fx, fy)
+        _lib.check(rc, "tcfd_fvm_plan_create")
+        self.handle = handle
+        self._ws: Optional[torch.Tensor] = None
+        self._finalizer = weakref.finalize(self, self.lib.tcfd_fvm_plan_destroy, handle)
+
+    def workspace(self, batch: int) -> torch.Tensor:
+        need = self.lib.tcfd_fvm_workspace_bytes(self.handle, batch)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _prep(self, ux, uy):
+        if not ux.is_cuda or ux.device != self.device:
+            raise _lib.TcfdError(f"expected tensors on {self.device} (torch-cfd_amd has no CPU fallback), got {ux.device}")
+        if ux.shape[-2:] != (self.n, self.n) or ux.ndim not in (2, 3):
+            raise ValueError(f"expected (n, n) or (B, n, n) velocity components with n = {self.n}, got {tuple(ux.shape)}")
+        ux = ux.detach().to(self.dtype).contiguous()
+        uy = uy.detach().to(self.dtype).contiguous()
+        return ux, uy, ux.numel() // (self.n * self.n)
+
+    def explicit_terms(self, ux, uy, dt: float):
+        ux, uy, batch = self._prep(ux, uy)
+        kx, ky = torch.empty_like(ux), torch.empty_like(uy)
+        with torch.cuda.device(self.device):
+            rc = self.lib.tcfd_fvm_explicit_terms(self.handle, ux.data_ptr(), uy.data_ptr(), kx.data_ptr(), ky.data_ptr(),
+                                                  batch, float(dt), self._stream())
+        _lib.check(rc, "tcfd_fvm_explicit_terms")
+        return kx, ky
+
+    def project(self, ux, uy):
+        ux, uy, batch = self._prep(ux, uy)
+        ox, oy = torch.empty_like(ux), torch.empty_like(uy)
+        ws = self.workspace(batch)
+        with torch.cuda.device(self.device):
+            rc = self.lib.tcfd_fvm_project(self.handle, ux.data_ptr(), uy.data_ptr(), ox.data_ptr(), oy.data_ptr(), batch,
+                                           ws.data_ptr(), ws.numel(), self._stream())
+        _lib.check(rc, "tcfd_fvm_project")
+        return ox, oy
+
+    def step(self, ux, uy, dt: float, a: Sequence[float], b: Sequence[float], steps: int):
+        ux, uy, batch = self._prep(ux, uy)
+        ox, oy = torch.empty_like(ux), torch.empty_like(uy)
+        ws = self.workspace(batch)
+        with torch.cuda.device(self.device):
+            rc = self.lib.tcfd_fvm_step(self.handle, ux.data_ptr(), uy.data_ptr(), ox.data_ptr(), oy.data_ptr(), batch,
+                                        int(steps), len(b), _lib.darray(a) if len(a) else None, _lib.darray(b), float(dt),
+                                        ws.data_ptr(), ws.numel(), self._stream())
+        _lib.check(rc, "tcfd_fvm_step")
+        return ox, oy
+
+
+# ----------------------------------------------------------------------------- pressure projection
+def laplacian_matrix(n: int, step: float, dtype=None) -> torch.Tensor:
+    """Dense periodic 1-D finite-difference Laplacian (torch_cfd/finite_differences.py:167-193)."""
+    column = torch.zeros(n, dtype=dtype)
+    column[0] = -2 / step**2
+    column[1] = column[-1] = 1 / step**2
+    idx = (n - torch.arange(n)[None].T + torch.arange(n)[None]) % n
+    return torch.gather(column[None, ...].expand(n, -1), 1, idx)
+
+
+def _circulant_eigenvalues(n: int, step: float, half: bool, dtype) -> torch.Tensor:
+    """Eigenvalues of the periodic FD Laplacian = the DFT of its first column, in closed form:
+    ``-2 / h^2 + 2 cos(2 pi k / n) / h^2`` (k < n, or k <= n / 2 for the half spectrum)."""
+    k = torch.arange(n // 2 + 1 if half else n, dtype=torch.float64)
+    lam = (-2 / step**2) + (2 / step**2) * torch.cos(2 * math.pi * k / n)
+    lam[0] = 0.0   # the column sums to zero exactly: -2/h^2 + 1/h^2 + 1/h^2
+    return lam.to(dtype)
+
+
+class Pseudoinverse(nn.Module):
+    """Pseudo-inverse of the periodic FD Laplacian by rfft2 diagonalisation (pressure.py:153, implementation "rfft").
+    Buffers as the reference's: ``laplacians`` (2, n, n), ``inverse`` (n, n/2 + 1) complex, ``eigenvectors``.
+    The eigenvalue cut-off is ``10 eps(dtype)`` -- float32 by default whatever the field precision, as there."""
+
+    def __init__(self, grid: Grid, bc=None, dtype: torch.dtype = torch.float32, laplacians: Optional[torch.Tensor] = None,
+                 cutoff: Optional[float] = None, **unused):
+        super().__init__()
+        _check_periodic(bc)
+        self.grid = grid
+        self.cutoff = cutoff or 10 * torch.finfo(dtype).eps
+        n, h = grid.shape[0], _square_step(grid)
+        if n % 2:
+            raise NotImplementedError(f"n = {n}: the rfft pseudo-inverse needs an even grid")
+        if laplacians is None:
+            laplacians = torch.stack([laplacian_matrix(m, s) for m, s in zip(grid.shape, grid.step)])
+        self.register_buffer("laplacians", laplacians, persistent=True)
+        real = laplacians.dtype
+        cplx = torch.complex128 if real == torch.float64 else torch.complex64
+        summed = _circulant_eigenvalues(n, h, False, real)[:, None] + _circulant_eigenvalues(n, h, True, real)[None, :]
+        summed = summed.to(cplx)
+        inverse = torch.where(torch.abs(summed) > self.cutoff, 1 / summed, 0)
+        self.register_buffer("inverse", inverse, persistent=True)
+        self.register_buffer("eigenvectors", torch.tensor([1.0] * grid.ndim), persistent=True)
+
+
+class PressureProjection(nn.Module):
+    """``u - grad q`` with ``q = pinv(L) div u``: backward-difference divergence, pseudo-inverse by the HIP rfft2 /
+    irfft2 kernels, forward-difference gradient (pressure.py:68-106).  Periodic boundaries only."""
+
+    def __init__(self, grid: Grid, bc=None, dtype: torch.dtype = torch.float32, laplacians: Optional[torch.Tensor] = None,
+                 **unused):
+        super().__init__()
+        _check_periodic(bc)
+        self.grid = grid
+        self.dtype = dtype
+        if laplacians is None:
+            laplacians = torch.stack([laplacian_matrix(m, s) for m, s in zip(grid.shape, grid.step)])
+        self.register_buffer("laplacians", laplacians, persistent=True)
+        self.solver = Pseudoinverse(grid, bc, dtype=dtype, laplacians=self.laplacians)
+        self._plans: Dict[tuple, _FvmPlan] = {}
+
+    def _plan(self, dtype, device) -> _FvmPlan:
+        inv = self.solver.inverse
+        key = (torch.device(device), dtype, id(inv), inv._version)
+        plan = self._plans.get(key)
+        if plan is None:
+            self._plans.clear()
+            plan = _FvmPlan(self.grid.shape[0], dtype, device, _square_step(self.grid), 0.0, 0.0, inv, None)
+            self._plans[key] = plan
+        return plan
+
+    def forward(self, v):
+        ux, uy = _as_pair(v)
+        return self._plan(ux.dtype, ux.device).project(ux, uy)
+
+
+# ----------------------------------------------------------------------------- the equation
+class NavierStokes2DFVMProjection(nn.Module):
+    """Incompressible Navier-Stokes on the MAC grid: explicit RK stages of
+    ``du/dt = -(u . grad) u (van Leer) + nu / density lap u + forcing / density - drag u``, each stage state and the result
+    projected onto discretely divergence-free fields (torch_cfd/fvm.py:334).
+
+    ``forward(u, dt, steps=1)`` runs ``steps`` steps of ``solver`` (an ``RKStepper``) in one device call and returns the
+    pair ``(ux, uy)``; ``explicit_terms(u, dt)`` and ``pressure_projection(u)`` are the two halves on their own."""
+
+    def __init__(self, viscosity: float, grid: Grid, bcs=None, drag: float = 0.0, density: float = 1.0, forcing=None,
+                 solver: Optional[RKStepper] = None, **kwargs):
+        super().__init__()
+        _check_periodic(bcs)
+        _square_step(grid)
+        self.viscosity = viscosity
+        self.density = density
+        self.grid = grid
+        self.bcs = bcs
+        self.drag = drag
+        self.forcing = forcing
+        self.solver = solver
+        self._projection = PressureProjection(grid=grid)
+        self._plans: Dict[tuple, _FvmPlan] = {}
+
+    def _force_tables(self):
+        """(fx, fy) / density at the staggered offsets, sampled once per plan (the forcing is state independent)."""
+        if self.forcing is None:
+            return None
+        f = self.forcing(self.grid, None)
+        return tuple(_tensor_of(c).detach().to("cpu", torch.float64) / self.density for c in f)
+
+    def _plan(self, dtype, device) -> _FvmPlan:
+        inv = self._projection.solver.inverse
+        fkey = None if self.forcing is None else getattr(self.forcing, "fingerprint", lambda: id(self.forcing))()
+        key = (torch.device(device), dtype, self.grid.shape[0], float(self.viscosity), float(self.density), float(self.drag),
+               fkey, id(inv), inv._version)
+        plan = self._plans.get(key)
+        if plan is None:
+            self._plans.clear()
+            plan = _FvmPlan(self.grid.shape[0], dtype, device, _square_step(self.grid), self.viscosity / self.density,
+                            self.drag, inv, self._force_tables())
+            self._plans[key] = plan
+        return plan
+
+    def explicit_terms(self, u, dt: float):
+        ux, uy = _as_pair(u)
+        return self._plan(ux.dtype, ux.device).explicit_terms(ux, uy, dt)
+
+    def pressure_projection(self, u):
+        return self._projection(u)
+
+    def advance(self, u, dt: float, steps: int = 1, solver: Optional[RKStepper] = None):
+        solver = self.solver if solver is None else solver
+        if solver is None:
+            raise ValueError("NavierStokes2DFVMProjection: no RKStepper (pass solver=RKStepper.from_method(...))")
+        solver._check_no_grad()
+        ux, uy = _as_pair(u)
+        a, b = solver.weights(dt)
+        return self._plan(ux.dtype, ux.device).step(ux, uy, dt, a, b, steps)
+
+    def forward(self, u, dt: float, steps: int = 1):
+        return self.advance(u, dt, steps=steps)
+
+
+def get_trajectory_fvm(equation: NavierStokes2DFVMProjection, u0, dt: float, num_steps: int, record_every_steps: int):
+    """Run ``num_steps`` steps from ``u0`` and record the state after every ``record_every_steps`` of them: returns
+    ``(ux, uy)`` stacked over the records on the dimension before the grid ((T, n, n), or (B, T, n, n) for a batch).
+    The notebook's inner / outer loop without a host synchronisation per step."""
+    if record_every_steps <= 0 or num_steps % record_every_steps:
+        raise ValueError(f"num_steps = {num_steps} is not a positive multiple of record_every_steps = {record_every_steps}")
+    u = _as_pair(u0)
+    xs, ys = [], []
+    for _ in range(num_steps // record_every_steps):
+        u = equation(u, dt, steps=record_every_steps)
+        xs.append(u[0])
+        ys.append(u[1])
+    return torch.stack(xs, dim=-3), torch.stack(ys, dim=-3)
