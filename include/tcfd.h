@@ -56,7 +56,7 @@ typedef struct tcfd_ns2d_plan tcfd_ns2d_plan;
 typedef struct tcfd_fno_plan tcfd_fno_plan;
 typedef struct tcfd_fvm_plan tcfd_fvm_plan;
 
-#define TCFD_ABI_VERSION 8   /* what tcfd_version() of a library built from THIS header returns */
+#define TCFD_ABI_VERSION 9   /* what tcfd_version() of a library built from THIS header returns */
 
 #ifndef TCFD_H_TYPES_ONLY   /* (the library's second compilation unit wants the types without the prototypes) */
 
@@ -64,7 +64,8 @@ const char* tcfd_last_error(void);
 /* ABI revision of the library that was loaded.  It changes whenever an entry point changes its argument list or the
  * meaning of an argument (round 3 turned the float scalars of the tcfd_fno_* calls into doubles and gave tcfd_fno_contract
  * a dtype: revision 1 -> 4; round 5: 6, tcfd_fno_pointwise_pre / _bwd_saved / _profile_*, tcfd_fno_spectral_conv_pointwise
- * removed; 7: tcfd_sobolev_loss_backward, tcfd_fno_forward_trunc_kt / _inverse_trunc_kt added -- a host written against 7 needs them).  A host compares it with the TCFD_ABI_VERSION it was written against BEFORE the
+ * removed; 7: tcfd_sobolev_loss_backward, tcfd_fno_forward_trunc_kt / _inverse_trunc_kt added -- a host written against 7 needs them;
+ * 8: tcfd_fvm_*; 9: tcfd_fvm_explicit_terms_vjp, tcfd_fvm_step_vjp_workspace_bytes, tcfd_fvm_step_vjp).  A host compares it with the TCFD_ABI_VERSION it was written against BEFORE the
  * first call: a stale prebuilt library would otherwise be called with the wrong argument layout and return garbage
  * (torch-cfd_amd/_lib.py::load does). */
 int tcfd_version(void);
@@ -513,6 +514,21 @@ int tcfd_fvm_project(const tcfd_fvm_plan* plan, const void* ux, const void* uy, 
 int tcfd_fvm_step(const tcfd_fvm_plan* plan, const void* ux_in, const void* uy_in, void* ux_out, void* uy_out, long batch,
                   int steps, int nstages, const double* a, const double* b, double dt, void* workspace,
                   size_t workspace_bytes, void* stream);
+
+/* Vector-Jacobian products of the finite-volume solver (reverse mode; the projection is symmetric, so tcfd_fvm_project of a
+ * cotangent is its own VJP).  The derivatives follow the branches torch autograd takes through the reference's ops.
+ * explicit_terms_vjp: (out_x, out_y) = J^T (gx, gy), J the Jacobian of tcfd_fvm_explicit_terms at (ux, uy).  The outputs may
+ *   not alias an input.
+ * step_vjp: reverse of `steps` tcfd_fvm_step steps with the same tableau and dt.  saved[steps][2][batch][n][n] holds the
+ *   input of every step (the pair (ux, uy) of step s at saved + 2 s batch n n); (gx, gy) is the cotangent of the result of
+ *   the last step, (out_x, out_y) receives that of the input of the first.  out may alias g.  Each step's stage states are
+ *   recomputed from its saved input by the forward kernels.  Workspace: tcfd_fvm_step_vjp_workspace_bytes(plan, batch). */
+int tcfd_fvm_explicit_terms_vjp(const tcfd_fvm_plan* plan, const void* ux, const void* uy, const void* gx, const void* gy,
+                                void* out_x, void* out_y, long batch, double dt, void* stream);
+size_t tcfd_fvm_step_vjp_workspace_bytes(const tcfd_fvm_plan* plan, long batch);
+int tcfd_fvm_step_vjp(const tcfd_fvm_plan* plan, const void* saved, const void* gx, const void* gy, void* out_x, void* out_y,
+                      long batch, int steps, int nstages, const double* a, const double* b, double dt, void* workspace,
+                      size_t workspace_bytes, void* stream);
 
 #endif /* TCFD_H_TYPES_ONLY */
 

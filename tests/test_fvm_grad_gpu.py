@@ -1,0 +1,249 @@
+"""GPU tests of the finite-volume solver's reverse mode (the adjoint kernels of tcfd_fvm.hip, torch_cfd_amd/fvm_autograd.py)
+against the reference's autograd gradients (tests/golden/fvm_grad.npz) and torch autograd through tests/fvm_ops.py."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import fvm_ops as F
+from conftest import load_golden, rel_l2
+
+pytestmark = pytest.mark.gpu
+L = 2 * math.pi
+DEV = "cuda:0"
+METHODS = ("forward_euler", "midpoint", "heun_rk2", "classic_rk4")
+FP64_BOUND = 1e-10
+
+
+def _equation(n, method="classic_rk4", wave=4, dtype=torch.float32):
+    import torch_cfd_amd as tc
+
+    grid = tc.Grid(shape=(n, n), domain=((0, L), (0, L)))
+    forcing = tc.KolmogorovForcing(grid=grid, diam=L, wave_number=wave, offsets=grid.cell_faces)
+    return tc.NavierStokes2DFVMProjection(1e-3, grid, drag=0.1, forcing=forcing,
+                                          solver=tc.RKStepper.from_method(method=method, dtype=dtype))
+
+
+@pytest.fixture
+def fp64_default():
+    old = torch.get_default_dtype()
+    torch.set_default_dtype(torch.float64)
+    yield
+    torch.set_default_dtype(old)
+
+
+def _leaves(a, dtype=torch.float64):
+    t = torch.from_numpy(np.asarray(a)).to(DEV, dtype)
+    return t[..., 0, :, :].clone().requires_grad_(), t[..., 1, :, :].clone().requires_grad_()
+
+
+def _dot(out, cot):
+    return (out[0] * cot[..., 0, :, :]).sum() + (out[1] * cot[..., 1, :, :]).sum()
+
+
+def _vjp(fn, u, cot):
+    cot = torch.as_tensor(cot).to(DEV, u[0].dtype)
+    return torch.stack(torch.autograd.grad(_dot(fn(u), cot), u), dim=-3)
+
+
+def _ops_rollout(eq, n, k, dt, dtype=torch.float64):
+    a, b = eq.solver.weights(dt)
+    force = tuple(f.to(DEV, dtype) for f in F.kolmogorov_staggered(n, 4))
+    inv = F.inverse_eigenvalues(n, L / n, dtype).to(DEV)
+
+    def run(u):
+        ux, uy = u
+        for _ in range(k):
+            ux, uy = F.step(ux, uy, dt, a, b, L / n, 1e-3, 0.1, force, inv)
+        return ux, uy
+    return run
+
+
+def test_explicit_terms_and_projection_vjps_against_the_reference(fp64_default):
+    g = load_golden("fvm_grad.npz")
+    eq = _equation(32)
+    dt = float(g["terms_dt"])
+    got = _vjp(lambda u: eq.explicit_terms(u, dt), _leaves(g["terms_u"]), g["terms_cot"])
+    err = rel_l2(got.cpu(), g["terms_explicit_vjp"])
+    print(f"explicit-terms VJP rel-L2 {err:.2e}")
+    assert err <= FP64_BOUND, err
+    got = _vjp(lambda u: eq.pressure_projection(u), _leaves(g["proj_u"]), g["terms_cot"])
+    err = rel_l2(got.cpu(), g["proj_vjp"])
+    print(f"projection VJP rel-L2 {err:.2e}")
+    assert err <= FP64_BOUND, err
+
+
+@pytest.mark.parametrize("case", ["n16_b2", "n32_b1"])
+@pytest.mark.parametrize("method", METHODS)
+def test_step_gradients_against_the_reference(case, method, fp64_default):
+    """1 and 3 steps of every named method, Kolmogorov forcing, drag 0.1; the batch of two is one device call."""
+    g = load_golden("fvm_grad.npz")
+    n = int(case[1:3])
+    eq = _equation(n, method)
+    dt = float(g[f"{case}_dt"])
+    for k in (1, 3):
+        got = _vjp(lambda u: eq(u, dt, steps=k), _leaves(g[f"{case}_u0"]), g[f"{case}_cot"])
+        err = rel_l2(got.cpu(), g[f"{case}_{method}_{k}"])
+        print(f"{case} {method} {k} steps: rel-L2 {err:.2e}")
+        assert err <= FP64_BOUND, (k, err)
+
+
+def test_fp32_gradient_within_the_reference_fp32_spread(fp64_default):
+    """fp32 fields: the spread is the reference's own fp32 gradient against the fp64 gradient at the same (fp32) inputs."""
+    g = load_golden("fvm_grad.npz")
+    dt = float(g["f32_dt"])
+    eq = _equation(32)
+    exact = _vjp(_ops_rollout(eq, 32, 3, dt), _leaves(g["f32_u0"]), g["f32_cot"]).cpu()
+    spread = rel_l2(g["f32_classic_rk4_3"], exact)
+    got = _vjp(lambda u: eq(u, dt, steps=3), _leaves(g["f32_u0"], torch.float32), g["f32_cot"])
+    assert got.dtype == torch.float32
+    err = rel_l2(got.cpu(), exact)
+    print(f"fp32: rel-L2 {err:.2e} against fp64, the reference's fp32 {spread:.2e}")
+    assert err <= 2 * spread, (err, spread)
+
+
+@pytest.mark.parametrize("n, batch, steps", [(256, 4, 20), (1024, 2, 2)])
+def test_gradient_against_autograd_through_the_restatement(n, batch, steps, fp64_default):
+    from torch_cfd_amd import initial_conditions as ic
+    import torch_cfd_amd as tc
+
+    grid = tc.Grid(shape=(n, n), domain=((0, L), (0, L)))
+    ux, uy = ic.filtered_velocity_field(grid, 2.0, 3.0, random_state=0, device=DEV, batch_seeds=list(range(batch)))
+    eq = _equation(n)
+    dt = tc.stable_time_step(dx=L / n, max_velocity=2.0, max_courant_number=0.5, viscosity=1e-3)
+    cot = torch.randn(batch, 2, n, n, generator=torch.Generator().manual_seed(n), dtype=torch.float64).to(DEV)
+    u = (ux.detach().clone().requires_grad_(), uy.detach().clone().requires_grad_())
+    got = _vjp(lambda v: eq(v, dt, steps=steps), u, cot)
+    want = _vjp(_ops_rollout(eq, n, steps, dt), u, cot)
+    err = rel_l2(got.cpu(), want.cpu())
+    print(f"{n}^2 x {batch}, {steps} steps: rel-L2 {err:.2e} against autograd through fvm_ops")
+    assert err <= 1e-10, err
+
+
+def test_projection_dot_product(fp64_default):
+    """<P a, b> = <a, VJP_P(b)> at n = 64, batch 2."""
+    eq = _equation(64)
+    gen = torch.Generator().manual_seed(5)
+    a = torch.randn(2, 2, 64, 64, generator=gen).to(DEV)
+    b = torch.randn(2, 2, 64, 64, generator=gen).to(DEV)
+    with torch.no_grad():
+        pa = eq.pressure_projection((a[:, 0], a[:, 1]))
+    vb = _vjp(lambda u: eq.pressure_projection(u), (a[:, 0].clone().requires_grad_(), a[:, 1].clone().requires_grad_()), b)
+    lhs = _dot(pa, b).item()
+    rhs = (a * vb).sum().item()
+    assert abs(lhs - rhs) <= 1e-12 * a.norm().item() * b.norm().item(), (lhs, rhs)
+
+
+def test_explicit_terms_directional_derivative(fp64_default):
+    """<VJP(lam), v> against the central difference <lam, (F(u + e v) - F(u - e v)) / 2e> on a smooth field."""
+    from torch_cfd_amd import initial_conditions as ic
+    import torch_cfd_amd as tc
+
+    n = 64
+    grid = tc.Grid(shape=(n, n), domain=((0, L), (0, L)))
+    ux, uy = ic.filtered_velocity_field(grid, 2.0, 3.0, random_state=3, device=DEV)
+    ux, uy = ux.detach(), uy.detach()
+    eq = _equation(n)
+    dt = tc.stable_time_step(dx=L / n, max_velocity=2.0, max_courant_number=0.5, viscosity=1e-3)
+    x = (torch.arange(n, dtype=torch.float64, device=DEV) + 0.5) * (L / n)
+    v = torch.stack([torch.sin(x)[:, None] * torch.cos(2 * x)[None, :], torch.cos(3 * x)[:, None] * torch.sin(x)[None, :]])
+    lam = torch.stack([torch.cos(x)[:, None] * torch.cos(x)[None, :], torch.sin(2 * x)[:, None] * torch.cos(x)[None, :]])
+    vjp = _vjp(lambda u: eq.explicit_terms(u, dt), (ux.clone().requires_grad_(), uy.clone().requires_grad_()), lam)
+    e = 1e-6
+    with torch.no_grad():
+        fp = eq.explicit_terms((ux + e * v[0], uy + e * v[1]), dt)
+        fm = eq.explicit_terms((ux - e * v[0], uy - e * v[1]), dt)
+    fd = (_dot(fp, lam) - _dot(fm, lam)).item() / (2 * e)
+    ad = (vjp * v).sum().item()
+    print(f"directional derivative: VJP {ad:.12e}, central difference {fd:.12e}")
+    assert abs(ad - fd) <= 1e-6 * abs(fd), (ad, fd)
+
+
+def test_steps_k_backward_is_bit_equal_to_k_chained_calls_and_reproducible(fp64_default):
+    g = load_golden("fvm_grad.npz")
+    eq = _equation(32)
+    dt = float(g["n32_b1_dt"])
+    cot = torch.from_numpy(g["n32_b1_cot"])
+
+    def chained(u):
+        for _ in range(4):
+            u = eq(u, dt)
+        return u
+    once = _vjp(lambda u: eq(u, dt, steps=4), _leaves(g["n32_b1_u0"]), cot)
+    again = _vjp(lambda u: eq(u, dt, steps=4), _leaves(g["n32_b1_u0"]), cot)
+    calls = _vjp(chained, _leaves(g["n32_b1_u0"]), cot)
+    assert torch.equal(once, again)
+    assert torch.equal(once, calls)
+
+
+def test_forward_under_grad_is_bit_equal_to_no_grad(fp64_default):
+    g = load_golden("fvm_grad.npz")
+    eq = _equation(16, "heun_rk2")
+    dt = float(g["n16_b2_dt"])
+    u = _leaves(g["n16_b2_u0"])
+    out = eq(u, dt, steps=5)
+    assert out[0].requires_grad and out[1].requires_grad
+    with torch.no_grad():
+        ref = eq((u[0].detach(), u[1].detach()), dt, steps=5)
+    assert torch.equal(out[0].detach(), ref[0]) and torch.equal(out[1].detach(), ref[1])
+
+
+def test_one_component_loss_and_one_leaf(fp64_default):
+    """A loss that reads ux only (no cotangent for uy), and a state where only uy requires grad."""
+    g = load_golden("fvm_grad.npz")
+    eq = _equation(32)
+    dt = float(g["n32_b1_dt"])
+    u = _leaves(g["n32_b1_u0"])
+    got = torch.autograd.grad(eq(u, dt, steps=2)[0].square().sum(), u)
+    want = torch.autograd.grad(_ops_rollout(eq, 32, 2, dt)(u)[0].square().sum(), u)
+    for a, b in zip(got, want):
+        assert rel_l2(a.cpu(), b.cpu()) <= 1e-12
+    ux, uy = u[0].detach(), u[1].detach().requires_grad_()
+    (gy,) = torch.autograd.grad(eq((ux, uy), dt)[1].sum(), uy)
+    (wy,) = torch.autograd.grad(_ops_rollout(eq, 32, 1, dt)((ux, uy))[1].sum(), uy)
+    assert rel_l2(gy.cpu(), wy.cpu()) <= 1e-12
+
+
+def test_trajectory_is_differentiable(fp64_default):
+    import torch_cfd_amd as tc
+
+    g = load_golden("fvm_grad.npz")
+    eq = _equation(16)
+    dt = float(g["n16_b2_dt"])
+    u = _leaves(g["n16_b2_u0"])
+    tx, ty = tc.get_trajectory_fvm(eq, u, dt, num_steps=6, record_every_steps=2)
+    assert tx.shape == (2, 3, 16, 16)
+    w = torch.linspace(0.5, 1.5, 3, device=DEV, dtype=torch.float64)[None, :, None, None]
+    got = torch.autograd.grad((tx * w).sum() + (ty * w).square().sum(), u)
+    run = _ops_rollout(eq, 16, 2, dt)
+    v, xs, ys = u, [], []
+    for _ in range(3):
+        v = run(v)
+        xs.append(v[0])
+        ys.append(v[1])
+    want = torch.autograd.grad((torch.stack(xs, 1) * w).sum() + (torch.stack(ys, 1) * w).square().sum(), u)
+    for a, b in zip(got, want):
+        assert rel_l2(a.cpu(), b.cpu()) <= 1e-12
+
+
+def test_double_backward_raises(fp64_default):
+    g = load_golden("fvm_grad.npz")
+    eq = _equation(16)
+    dt = float(g["n16_b2_dt"])
+    for fn in (lambda u: eq(u, dt, steps=2), lambda u: eq.explicit_terms(u, dt), lambda u: eq.pressure_projection(u)):
+        u = _leaves(g["n16_b2_u0"])
+        out = fn(u)
+        (gx, _) = torch.autograd.grad(out[0].square().sum() + out[1].sum(), u, create_graph=True)
+        with pytest.raises(RuntimeError):
+            torch.autograd.grad(gx.square().sum(), u)
+
+
+def test_requires_grad_tableau_still_raises_with_a_differentiable_state(fp64_default):
+    import torch_cfd_amd as tc
+
+    g = load_golden("fvm_grad.npz")
+    eq = _equation(16)
+    s = tc.RKStepper.from_method(method="classic_rk4", requires_grad=True)
+    with pytest.raises(NotImplementedError):
+        s.forward(_leaves(g["n16_b2_u0"]), float(g["n16_b2_dt"]), equation=eq)

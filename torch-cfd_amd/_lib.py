@@ -27,7 +27,7 @@ LIB_PATH = os.path.join(CSRC, LIB_NAME)
 SOURCES = ("tcfd_ns2d.hip", "tcfd_fno.hip", "tcfd_fno_pw.hip", "tcfd_fno_tiles.hip", "tcfd_loss.hip", "tcfd_fvm.hip")
 
 TCFD_C64, TCFD_C128 = 0, 1
-ABI_VERSION = 8   # TCFD_ABI_VERSION of include/tcfd.h the SIGNATURES table below was written against
+ABI_VERSION = 9   # TCFD_ABI_VERSION of include/tcfd.h the SIGNATURES table below was written against
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -195,6 +195,9 @@ SIGNATURES = {
     "tcfd_fvm_explicit_terms": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _d, _vp]),
     "tcfd_fvm_project": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _vp, _sz, _vp]),
     "tcfd_fvm_step": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _i, _i, _dp, _dp, _d, _vp, _sz, _vp]),
+    "tcfd_fvm_explicit_terms_vjp": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _d, _vp]),
+    "tcfd_fvm_step_vjp_workspace_bytes": (_sz, [_vp, _l]),
+    "tcfd_fvm_step_vjp": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _dp, _dp, _d, _vp, _sz, _vp]),
 }
 
 

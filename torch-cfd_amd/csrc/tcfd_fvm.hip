@@ -12,6 +12,12 @@
 //   tcfd_rfft2 -> k_fvm_mul (x inverse eigenvalues) -> tcfd_irfft2: q of the next stage
 // The transforms are the spectral solver's kernels (tcfd_ns2d.hip) on a table-free plan held by the FVM plan.
 //
+// Reverse of one step (tcfd_fvm_step_vjp; u_bar is the cotangent of the step's result, overwritten by that of its input):
+//   stages 0 .. s-2 of the forward (k_fvm_stage + projection) rebuild the stage states u_1 .. u_{s-1} from the saved u0
+//   projection of u_bar, its apply pass k_fvm_apply_adj: mu = P u_bar;  u_bar = mu;  kbar_j = b_j mu
+//   for i = s-1 .. 0:  k_fvm_stage_vjp  g_i = J_F(u_i)^T kbar_i  (i = 0: added into u_bar; done)
+//                      projection of g_i, k_fvm_apply_adj: mu_i = P g_i;  u_bar += mu_i;  kbar_j (+)= a_ij mu_i (j < i)
+//
 // Every arithmetic expression restates the reference's operation order; floating-point contraction is off in this file
 // so that a * b + c rounds twice as the reference's tensor ops do.
 #include <hip/hip_runtime.h>
@@ -222,6 +228,193 @@ __global__ void __launch_bounds__(256) k_fvm_apply(const T* __restrict__ px, con
     oy[p] = py[p] - gy;
 }
 
+// ---------------------------------------------------------------- adjoint (vector-Jacobian products)
+// The projection is symmetric (P = I - G pinv(L) D with D = -G^T, L = D G), so its VJP is the projection of the cotangent.
+// The explicit terms' VJP is gathered: the thread of cell (i, j) recomputes the partial derivatives of every face flux whose
+// stencil reads ux[i][j] or uy[i][j] and sums (cotangent of the flux) * (partial).  No atomics: the result is bitwise
+// reproducible.
+
+// cotangents of the inputs (cm, c0, c1, c2, w) of tvd_flux, given the cotangent lam of its result.  The derivative follows
+// the branches torch autograd takes through the reference's ops: the selections w > 0 and r > 0 pass no gradient, w still
+// enters through the Courant number and the final product; safe_div's constant denominator 1 (d == 0) takes none.
+template <typename T>
+struct FluxBar {
+    T cm, c0, c1, c2, w;
+};
+
+template <typename T>
+__device__ __forceinline__ FluxBar<T> tvd_flux_vjp(T cm, T c0, T c1, T c2, T w, T cfl, T lam) {
+    const bool pos = w > T(0);
+    const T clow = pos ? c0 : c1;
+    const T cr = cfl * w;
+    const T d = c1 - c0;
+    const T alpha = T(0.5) * (T(1) - cr);   // hp = c0 + alpha d
+    const T beta = T(0.5) * (T(1) + cr);    // hn = c1 - beta d
+    const T chigh = pos ? c0 + alpha * d : c1 - beta * d;
+    const bool dnz = d != T(0);
+    const T dd = dnz ? d : T(1);
+    const T r = (pos ? c0 - cm : c2 - c1) / dd;
+    const bool lim = r > T(0);
+    const T rp1 = T(1) + r;
+    const T phi = lim ? (T(2) * r) / rp1 : T(0);
+    const T dphi = lim ? T(2) / (rp1 * rp1) : T(0);
+    const T ci = clow - (clow - chigh) * phi;
+    // flux = ci w,  ci = clow (1 - phi) + chigh phi
+    const T bci = lam * w;
+    const T bclow = bci * (T(1) - phi);
+    const T bchigh = bci * phi;
+    const T br = -(bci * (clow - chigh)) * dphi;
+    const T bnum = br / dd;
+    T bd = dnz ? -(br * r) / dd : T(0);      // through the denominator of r
+    FluxBar<T> g;
+    g.w = lam * ci + bchigh * (T(-0.5) * cfl * d);   // d chigh / d w = -cfl d / 2 in both branches
+    g.cm = T(0);
+    g.c2 = T(0);
+    if (pos) {
+        g.c0 = bclow + bchigh + bnum;
+        g.c1 = T(0);
+        g.cm = -bnum;
+        bd = bd + bchigh * alpha;
+    } else {
+        g.c0 = T(0);
+        g.c1 = bclow + bchigh - bnum;
+        g.c2 = bnum;
+        bd = bd - bchigh * beta;
+    }
+    g.c1 = g.c1 + bd;
+    g.c0 = g.c0 - bd;
+    return g;
+}
+
+// (lx, ly) = J^T (LX, LY) of explicit_point at cell (i, j): X / Y the state, LX / LY the cotangent of (kx, ky).
+// Face fluxes (p, q any cell, all indices periodic):
+//   FX[p][q] ux along axis 0: tvd_flux(X[p-1][q], X[p][q], X[p+1][q], X[p+2][q], half(X[p][q], X[p+1][q]))
+//   GX[p][q] ux along axis 1: tvd_flux(X[p][q-1], X[p][q], X[p][q+1], X[p][q+2], half(Y[p][q], Y[p+1][q]))
+//   FY[p][q] uy along axis 0: tvd_flux(Y[p-1][q], Y[p][q], Y[p+1][q], Y[p+2][q], half(X[p][q], X[p][q+1]))
+//   GY[p][q] uy along axis 1: tvd_flux(Y[p][q-1], Y[p][q], Y[p][q+1], Y[p][q+2], half(Y[p][q], Y[p][q+1]))
+// kx[p][q] = -((FX[p][q] - FX[p-1][q]) / h + (GX[p][q] - GX[p][q-1]) / h) + ..., so the cotangent of FX[p][q] is
+// (LX[p+1][q] - LX[p][q]) / h, and likewise for the others.  X[i][j] is read by FX[i-2 .. i+1][j], GX[i][j-2 .. j+1] and
+// the face velocities of FY[i][j-1 .. j]; Y[i][j] by FY[i-2 .. i+1][j], GY[i][j-2 .. j+1] and the face velocities of
+// GX[i-1 .. i][j]: 18 flux evaluations per cell, against the forward's 8.
+template <typename T>
+__device__ __forceinline__ void explicit_point_vjp(const T* __restrict__ X, const T* __restrict__ Y, const T* __restrict__ LX,
+                                                   const T* __restrict__ LY, int i, int j, int n, const StageConst<T>& s, T& lx,
+                                                   T& ly) {
+    auto at = [n](const T* p, int a, int b) { return p[(size_t)wrap(a, n) * n + wrap(b, n)]; };
+    auto cot = [&](const T* l, int a, int b, int a1, int b1) { return (at(l, a1, b1) - at(l, a, b)) / s.h; };
+    T gx = T(0), gy = T(0);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {   // FX[p][j], p = i - 2 + k: X[i][j] is its c2, c1, c0, cm
+        const int p = i - 2 + k;
+        const T c0 = at(X, p, j), c1 = at(X, p + 1, j);
+        const FluxBar<T> b = tvd_flux_vjp(at(X, p - 1, j), c0, c1, at(X, p + 2, j), half(c0, c1), s.cfl, cot(LX, p, j, p + 1, j));
+        gx = gx + (k == 0 ? b.c2 : k == 1 ? b.c1 + T(0.5) * b.w : k == 2 ? b.c0 + T(0.5) * b.w : b.cm);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {   // GX[i][q], q = j - 2 + k; Y[i][j] is the first half of the face velocity of GX[i][j]
+        const int q = j - 2 + k;
+        const FluxBar<T> b = tvd_flux_vjp(at(X, i, q - 1), at(X, i, q), at(X, i, q + 1), at(X, i, q + 2),
+                                          half(at(Y, i, q), at(Y, i + 1, q)), s.cfl, cot(LX, i, q, i, q + 1));
+        gx = gx + (k == 0 ? b.c2 : k == 1 ? b.c1 : k == 2 ? b.c0 : b.cm);
+        if (k == 2) gy = gy + T(0.5) * b.w;
+    }
+    {   // GX[i-1][j]: Y[i][j] is the second half of its face velocity
+        const FluxBar<T> b = tvd_flux_vjp(at(X, i - 1, j - 1), at(X, i - 1, j), at(X, i - 1, j + 1), at(X, i - 1, j + 2),
+                                          half(at(Y, i - 1, j), at(Y, i, j)), s.cfl, cot(LX, i - 1, j, i - 1, j + 1));
+        gy = gy + T(0.5) * b.w;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {   // FY[p][j], p = i - 2 + k; X[i][j] is the first half of the face velocity of FY[i][j]
+        const int p = i - 2 + k;
+        const FluxBar<T> b = tvd_flux_vjp(at(Y, p - 1, j), at(Y, p, j), at(Y, p + 1, j), at(Y, p + 2, j),
+                                          half(at(X, p, j), at(X, p, j + 1)), s.cfl, cot(LY, p, j, p + 1, j));
+        gy = gy + (k == 0 ? b.c2 : k == 1 ? b.c1 : k == 2 ? b.c0 : b.cm);
+        if (k == 2) gx = gx + T(0.5) * b.w;
+    }
+    {   // FY[i][j-1]: X[i][j] is the second half of its face velocity
+        const FluxBar<T> b = tvd_flux_vjp(at(Y, i - 1, j - 1), at(Y, i, j - 1), at(Y, i + 1, j - 1), at(Y, i + 2, j - 1),
+                                          half(at(X, i, j - 1), at(X, i, j)), s.cfl, cot(LY, i, j - 1, i + 1, j - 1));
+        gx = gx + T(0.5) * b.w;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {   // GY[i][q], q = j - 2 + k
+        const int q = j - 2 + k;
+        const T c0 = at(Y, i, q), c1 = at(Y, i, q + 1);
+        const FluxBar<T> b = tvd_flux_vjp(at(Y, i, q - 1), c0, c1, at(Y, i, q + 2), half(c0, c1), s.cfl, cot(LY, i, q, i, q + 1));
+        gy = gy + (k == 0 ? b.c2 : k == 1 ? b.c1 + T(0.5) * b.w : k == 2 ? b.c0 + T(0.5) * b.w : b.cm);
+    }
+    // the 5-point Laplacian is symmetric: nu lap(L); drag: -drag L; the forcing does not depend on the state
+    const T l00x = at(LX, i, j), l00y = at(LY, i, j);
+    T lap_x = (T(-2) * l00x) * s.sum_s;
+    lap_x = lap_x + (at(LX, i - 1, j) + at(LX, i + 1, j)) * s.inv_h2;
+    lap_x = lap_x + (at(LX, i, j - 1) + at(LX, i, j + 1)) * s.inv_h2;
+    T lap_y = (T(-2) * l00y) * s.sum_s;
+    lap_y = lap_y + (at(LY, i - 1, j) + at(LY, i + 1, j)) * s.inv_h2;
+    lap_y = lap_y + (at(LY, i, j - 1) + at(LY, i, j + 1)) * s.inv_h2;
+    lx = gx + s.nu * lap_x;
+    ly = gy + s.nu * lap_y;
+    if (s.drag_on) {
+        lx = lx + l00x * s.neg_drag;
+        ly = ly + l00y * s.neg_drag;
+    }
+}
+
+// (ox, oy) = J_F(u)^T (lx, ly), or += with accumulate (stage 0 of the reverse step adds straight into the cotangent of u0)
+template <typename T>
+__global__ void __launch_bounds__(256) k_fvm_stage_vjp(const T* __restrict__ ux, const T* __restrict__ uy, const T* __restrict__ lx,
+                                                       const T* __restrict__ ly, T* __restrict__ ox, T* __restrict__ oy,
+                                                       int accumulate, StageConst<T> s, int n) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = blockIdx.y * blockDim.y + threadIdx.y;
+    if (i >= n || j >= n) return;
+    const size_t base = (size_t)blockIdx.z * n * n;
+    T gx, gy;
+    explicit_point_vjp(ux + base, uy + base, lx + base, ly + base, i, j, n, s, gx, gy);
+    const size_t p = base + (size_t)i * n + j;
+    if (accumulate) {
+        gx = ox[p] + gx;
+        gy = oy[p] + gy;
+    }
+    ox[p] = gx;
+    oy[p] = gy;
+}
+
+constexpr int MAXA = MAXT + 1;   // targets of an adjoint apply: the cotangent of u0 + one per stage
+
+template <typename T>
+struct AdjTargets {
+    T* x[MAXA];
+    T* y[MAXA];
+    T c[MAXA];
+    int mode[MAXA];   // 0: t = mu,  1: t = t + mu,  2: t = mu * c,  3: t = t + mu * c
+    int count;
+};
+
+// mu = g - grad q (the projection's apply pass on a cotangent), then every target (+)= (c) mu.  A target may alias g.
+template <typename T>
+__global__ void __launch_bounds__(256) k_fvm_apply_adj(const T* gx, const T* gy, const T* __restrict__ q, AdjTargets<T> tg, T h,
+                                                       int n) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = blockIdx.y * blockDim.y + threadIdx.y;
+    if (i >= n || j >= n) return;
+    const size_t base = (size_t)blockIdx.z * n * n;
+    const size_t p = base + (size_t)i * n + j;
+    const T q0 = q[p];
+    const T mx = gx[p] - (q[base + (size_t)wrap(i + 1, n) * n + j] - q0) / h;
+    const T my = gy[p] - (q[base + (size_t)i * n + wrap(j + 1, n)] - q0) / h;
+    for (int t = 0; t < tg.count; ++t) {
+        const int mode = tg.mode[t];
+        T vx = mode >= 2 ? mx * tg.c[t] : mx;
+        T vy = mode >= 2 ? my * tg.c[t] : my;
+        if (mode & 1) {
+            vx = tg.x[t][p] + vx;
+            vy = tg.y[t][p] + vy;
+        }
+        tg.x[t][p] = vx;
+        tg.y[t][p] = vy;
+    }
+}
+
 }  // namespace
 
 #if TCFD_UNIT == 1
@@ -306,6 +499,30 @@ int FVMFN(fvm_apply_launch)(const tcfd_fvm_plan* p, const void* px, const void* 
     return 0;
 }
 
+int FVMFN(fvm_stage_vjp_launch)(const tcfd_fvm_plan* p, const void* ux, const void* uy, const void* lx, const void* ly, void* ox,
+                                void* oy, int accumulate, long batch, double dt, hipStream_t st) {
+    hipLaunchKernelGGL(k_fvm_stage_vjp<Real>, cell_grid(p->n, batch), kCellBlock, 0, st, (const Real*)ux, (const Real*)uy,
+                       (const Real*)lx, (const Real*)ly, (Real*)ox, (Real*)oy, accumulate, stage_const(p, dt), p->n);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int FVMFN(fvm_apply_adj_launch)(const tcfd_fvm_plan* p, const void* gx, const void* gy, const void* q, void* const* tx,
+                                void* const* ty, const double* c, const int* mode, int count, long batch, hipStream_t st) {
+    AdjTargets<Real> tg;
+    tg.count = count;
+    for (int t = 0; t < MAXA; ++t) {
+        tg.x[t] = t < count ? (Real*)tx[t] : nullptr;
+        tg.y[t] = t < count ? (Real*)ty[t] : nullptr;
+        tg.c[t] = t < count ? (Real)c[t] : Real(0);
+        tg.mode[t] = t < count ? mode[t] : 0;
+    }
+    hipLaunchKernelGGL(k_fvm_apply_adj<Real>, cell_grid(p->n, batch), kCellBlock, 0, st, (const Real*)gx, (const Real*)gy,
+                       (const Real*)q, tg, (Real)p->h, p->n);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 #if TCFD_UNIT != 1
 // ================================================================ C ABI (unit 0)
 int fvm_stage_launch_f32(const tcfd_fvm_plan*, const void*, const void*, const void*, const void*, void*, void*, void* const*,
@@ -313,6 +530,10 @@ int fvm_stage_launch_f32(const tcfd_fvm_plan*, const void*, const void*, const v
 int fvm_div_launch_f32(const tcfd_fvm_plan*, const void*, const void*, void*, long, hipStream_t);
 int fvm_mul_launch_f32(const tcfd_fvm_plan*, void*, long, hipStream_t);
 int fvm_apply_launch_f32(const tcfd_fvm_plan*, const void*, const void*, const void*, void*, void*, long, hipStream_t);
+int fvm_stage_vjp_launch_f32(const tcfd_fvm_plan*, const void*, const void*, const void*, const void*, void*, void*, int, long,
+                             double, hipStream_t);
+int fvm_apply_adj_launch_f32(const tcfd_fvm_plan*, const void*, const void*, const void*, void* const*, void* const*,
+                             const double*, const int*, int, long, hipStream_t);
 
 namespace {
 
@@ -332,17 +553,31 @@ int apply_launch(const tcfd_fvm_plan* p, const void* px, const void* py, const v
                  hipStream_t st) {
     return is_f64(p) ? fvm_apply_launch_f64(p, px, py, q, ox, oy, batch, st) : fvm_apply_launch_f32(p, px, py, q, ox, oy, batch, st);
 }
+int stage_vjp_launch(const tcfd_fvm_plan* p, const void* ux, const void* uy, const void* lx, const void* ly, void* ox, void* oy,
+                     int accumulate, long batch, double dt, hipStream_t st) {
+    return is_f64(p) ? fvm_stage_vjp_launch_f64(p, ux, uy, lx, ly, ox, oy, accumulate, batch, dt, st)
+                     : fvm_stage_vjp_launch_f32(p, ux, uy, lx, ly, ox, oy, accumulate, batch, dt, st);
+}
+int apply_adj_launch(const tcfd_fvm_plan* p, const void* gx, const void* gy, const void* q, void* const* tx, void* const* ty,
+                     const double* c, const int* mode, int count, long batch, hipStream_t st) {
+    return is_f64(p) ? fvm_apply_adj_launch_f64(p, gx, gy, q, tx, ty, c, mode, count, batch, st)
+                     : fvm_apply_adj_launch_f32(p, gx, gy, q, tx, ty, c, mode, count, batch, st);
+}
 
-// workspace carve: [div | spectrum | q | transform scratch] for the projection, then the RK buffers of tcfd_fvm_step
+// workspace carve: [div | spectrum | q | transform scratch] for the projection, then the RK buffers of tcfd_fvm_step, or
+// those of tcfd_fvm_step_vjp: the stage states u_1 .. u_3, the stage cotangents kbar_0 .. kbar_3 and one g_i
 struct Carve {
     void *div, *spec, *q, *fftws;
     size_t fftws_bytes;
     void *u0x, *u0y, *ucx, *ucy;
     void *px[MAXT], *py[MAXT];
+    void *usx[MAXT - 1], *usy[MAXT - 1], *kbx[MAXT], *kby[MAXT], *gbx, *gby;
     size_t total;
 };
 
-Carve carve(const tcfd_fvm_plan* p, long batch, void* ws, bool rk) {
+constexpr int kProject = 0, kStep = 1, kStepVjp = 2;
+
+Carve carve(const tcfd_fvm_plan* p, long batch, void* ws, int kind) {
     Carve c{};
     char* b = (char*)ws;
     size_t off = 0;
@@ -357,7 +592,7 @@ Carve carve(const tcfd_fvm_plan* p, long batch, void* ws, bool rk) {
     c.q = take(F);
     c.fftws_bytes = tcfd_ns2d_workspace_bytes(p->fft, batch);
     c.fftws = take(c.fftws_bytes);
-    if (rk) {
+    if (kind == kStep) {
         c.u0x = take(F);
         c.u0y = take(F);
         c.ucx = take(F);
@@ -366,6 +601,17 @@ Carve carve(const tcfd_fvm_plan* p, long batch, void* ws, bool rk) {
             c.px[t] = take(F);
             c.py[t] = take(F);
         }
+    } else if (kind == kStepVjp) {
+        for (int t = 0; t < MAXT - 1; ++t) {
+            c.usx[t] = take(F);
+            c.usy[t] = take(F);
+        }
+        for (int t = 0; t < MAXT; ++t) {
+            c.kbx[t] = take(F);
+            c.kby[t] = take(F);
+        }
+        c.gbx = take(F);
+        c.gby = take(F);
     }
     c.total = off;
     return c;
@@ -381,8 +627,8 @@ int solve_q(const tcfd_fvm_plan* p, const void* px, const void* py, long batch, 
     return tcfd_irfft2(p->fft, c.spec, c.q, batch, c.fftws, c.fftws_bytes, st);
 }
 
-int check_ws(const tcfd_fvm_plan* p, long batch, void* ws, size_t ws_bytes, bool rk) {
-    const size_t need = carve(p, batch, nullptr, rk).total;
+int check_ws(const tcfd_fvm_plan* p, long batch, void* ws, size_t ws_bytes, int kind) {
+    const size_t need = carve(p, batch, nullptr, kind).total;
     if (!ws || ws_bytes < need) return FAIL(TCFD_EWORKSPACE, "fvm: workspace of %zu bytes, %zu needed", ws_bytes, need);
     return 0;
 }
@@ -446,7 +692,7 @@ void tcfd_fvm_plan_destroy(tcfd_fvm_plan* p) {
 
 size_t tcfd_fvm_workspace_bytes(const tcfd_fvm_plan* p, long batch) {
     if (!p || batch <= 0) return 0;
-    return carve(p, batch, nullptr, true).total;
+    return carve(p, batch, nullptr, kStep).total;
 }
 
 int tcfd_fvm_explicit_terms(const tcfd_fvm_plan* p, const void* ux, const void* uy, void* kx, void* ky, long batch,
@@ -458,10 +704,10 @@ int tcfd_fvm_explicit_terms(const tcfd_fvm_plan* p, const void* ux, const void* 
 int tcfd_fvm_project(const tcfd_fvm_plan* p, const void* ux, const void* uy, void* ux_out, void* uy_out, long batch,
                                   void* ws, size_t ws_bytes, void* stream) {
     if (!p || !ux || !uy || !ux_out || !uy_out || batch <= 0) return FAIL(TCFD_EINVAL, "fvm_project: bad argument");
-    int rc = check_ws(p, batch, ws, ws_bytes, false);
+    int rc = check_ws(p, batch, ws, ws_bytes, kProject);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const Carve c = carve(p, batch, ws, false);
+    const Carve c = carve(p, batch, ws, kProject);
     if ((rc = solve_q(p, ux, uy, batch, c, st))) return rc;
     return apply_launch(p, ux, uy, c.q, ux_out, uy_out, batch, st);
 }
@@ -476,10 +722,10 @@ int tcfd_fvm_step(const tcfd_fvm_plan* p, const void* ux_in, const void* uy_in, 
         for (int j = i; j < nstages; ++j)
             if (nstages > 1 && a[i * nstages + j] != 0.0)
                 return FAIL(TCFD_EINVAL, "fvm_step: a[%d][%d] != 0: only explicit (strictly lower) tableaux", i, j);
-    int rc = check_ws(p, batch, ws, ws_bytes, true);
+    int rc = check_ws(p, batch, ws, ws_bytes, kStep);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const Carve c = carve(p, batch, ws, true);
+    const Carve c = carve(p, batch, ws, kStep);
     const size_t F = field_bytes(p, batch);
     if (steps == 0) {
         if (ux_out != ux_in) HIP_TRY(hipMemcpyAsync(ux_out, ux_in, F, hipMemcpyDeviceToDevice, st));
@@ -527,6 +773,114 @@ int tcfd_fvm_step(const tcfd_fvm_plan* p, const void* ux_in, const void* uy_in, 
                 void* oy = last ? uy_out : c.u0y;
                 if ((rc = apply_launch(p, c.px[m - 1], c.py[m - 1], c.q, ox, oy, batch, st))) return rc;
             }
+        }
+    }
+    return 0;
+}
+
+int tcfd_fvm_explicit_terms_vjp(const tcfd_fvm_plan* p, const void* ux, const void* uy, const void* gx, const void* gy,
+                                void* out_x, void* out_y, long batch, double dt, void* stream) {
+    if (!p || !ux || !uy || !gx || !gy || !out_x || !out_y || batch <= 0)
+        return FAIL(TCFD_EINVAL, "fvm_explicit_terms_vjp: bad argument");
+    if (out_x == gx || out_x == gy || out_y == gx || out_y == gy || out_x == ux || out_x == uy || out_y == ux || out_y == uy)
+        return FAIL(TCFD_EINVAL, "fvm_explicit_terms_vjp: the output may not alias an input (the stencil reads neighbours)");
+    return stage_vjp_launch(p, ux, uy, gx, gy, out_x, out_y, 0, batch, dt, (hipStream_t)stream);
+}
+
+size_t tcfd_fvm_step_vjp_workspace_bytes(const tcfd_fvm_plan* p, long batch) {
+    if (!p || batch <= 0) return 0;
+    return carve(p, batch, nullptr, kStepVjp).total;
+}
+
+int tcfd_fvm_step_vjp(const tcfd_fvm_plan* p, const void* saved, const void* gx, const void* gy, void* out_x, void* out_y,
+                      long batch, int steps, int nstages, const double* a, const double* b, double dt, void* ws, size_t ws_bytes,
+                      void* stream) {
+    if (!p || !gx || !gy || !out_x || !out_y || batch <= 0 || steps < 0 || (steps > 0 && !saved) || !b || (nstages > 1 && !a))
+        return FAIL(TCFD_EINVAL, "fvm_step_vjp: bad argument");
+    if (nstages < 1 || nstages > MAXT) return FAIL(TCFD_EINVAL, "fvm_step_vjp: %d stages (1 .. %d supported)", nstages, MAXT);
+    for (int i = 0; i < nstages; ++i)
+        for (int j = i; j < nstages; ++j)
+            if (nstages > 1 && a[i * nstages + j] != 0.0)
+                return FAIL(TCFD_EINVAL, "fvm_step_vjp: a[%d][%d] != 0: only explicit (strictly lower) tableaux", i, j);
+    int rc = check_ws(p, batch, ws, ws_bytes, kStepVjp);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const Carve c = carve(p, batch, ws, kStepVjp);
+    const size_t F = field_bytes(p, batch);
+    // out holds the running cotangent: that of the result of step s on entry to its reverse, that of its input after
+    if (out_x != gx) HIP_TRY(hipMemcpyAsync(out_x, gx, F, hipMemcpyDeviceToDevice, st));
+    if (out_y != gy) HIP_TRY(hipMemcpyAsync(out_y, gy, F, hipMemcpyDeviceToDevice, st));
+    auto weight = [&](int m, int j) { return m < nstages ? a[m * nstages + j] : b[j]; };
+    const int S = nstages;
+    for (int s = steps - 1; s >= 0; --s) {
+        const char* u0x = (const char*)saved + (size_t)(2 * s) * F;
+        const char* u0y = u0x + F;
+        // stage states u_1 .. u_{S-1} (u_m in usx[m - 1]) by the forward's stages 0 .. S-2 and targets, the final sum left out
+        for (int j = 0; j + 1 < S; ++j) {
+            void* tx[MAXT];
+            void* ty[MAXT];
+            double cw[MAXT];
+            int mode[MAXT];
+            int count = 0;
+            for (int m = j + 1; m < S; ++m) {
+                const double w = weight(m, j);
+                bool started = false;
+                for (int jj = 0; jj < j; ++jj) started = started || weight(m, jj) != 0.0;
+                int md = 0;
+                if (w != 0.0) md = started ? 2 : 1;
+                else if (!started && j == m - 1) md = 3;
+                if (!md) continue;
+                tx[count] = c.usx[m - 1];
+                ty[count] = c.usy[m - 1];
+                cw[count] = w;
+                mode[count] = md;
+                ++count;
+            }
+            const void* sx = j == 0 ? (const void*)u0x : c.usx[j - 1];
+            const void* sy = j == 0 ? (const void*)u0y : c.usy[j - 1];
+            if ((rc = stage_launch(p, sx, sy, u0x, u0y, nullptr, nullptr, tx, ty, cw, mode, count, batch, dt, st))) return rc;
+            if ((rc = solve_q(p, c.usx[j], c.usy[j], batch, c, st))) return rc;
+            if ((rc = apply_launch(p, c.usx[j], c.usy[j], c.q, c.usx[j], c.usy[j], batch, st))) return rc;
+        }
+        // mu = P u_bar: u_bar = mu, kbar_j = b_j mu
+        bool live[MAXT] = {};
+        {
+            void* tx[MAXA];
+            void* ty[MAXA];
+            double cw[MAXA];
+            int mode[MAXA];
+            int count = 0;
+            tx[count] = out_x, ty[count] = out_y, cw[count] = 1.0, mode[count++] = 0;
+            for (int j = 0; j < S; ++j) {
+                if (b[j] == 0.0) continue;
+                tx[count] = c.kbx[j], ty[count] = c.kby[j], cw[count] = b[j], mode[count++] = 2;
+                live[j] = true;
+            }
+            if ((rc = solve_q(p, out_x, out_y, batch, c, st))) return rc;
+            if ((rc = apply_adj_launch(p, out_x, out_y, c.q, tx, ty, cw, mode, count, batch, st))) return rc;
+        }
+        for (int i = S - 1; i >= 0; --i) {
+            if (!live[i]) continue;   // no weight reads k_i: its cotangent is zero
+            if (i == 0) {
+                if ((rc = stage_vjp_launch(p, u0x, u0y, c.kbx[0], c.kby[0], out_x, out_y, 1, batch, dt, st))) return rc;
+                continue;
+            }
+            if ((rc = stage_vjp_launch(p, c.usx[i - 1], c.usy[i - 1], c.kbx[i], c.kby[i], c.gbx, c.gby, 0, batch, dt, st)))
+                return rc;
+            void* tx[MAXA];
+            void* ty[MAXA];
+            double cw[MAXA];
+            int mode[MAXA];
+            int count = 0;
+            tx[count] = out_x, ty[count] = out_y, cw[count] = 1.0, mode[count++] = 1;
+            for (int j = 0; j < i; ++j) {
+                const double w = a[i * S + j];
+                if (w == 0.0) continue;
+                tx[count] = c.kbx[j], ty[count] = c.kby[j], cw[count] = w, mode[count++] = live[j] ? 3 : 2;
+                live[j] = true;
+            }
+            if ((rc = solve_q(p, c.gbx, c.gby, batch, c, st))) return rc;
+            if ((rc = apply_adj_launch(p, c.gbx, c.gby, c.q, tx, ty, cw, mode, count, batch, st))) return rc;
         }
     }
     return 0;

@@ -8,7 +8,11 @@ The velocity is a pair ``(ux, uy)`` of ``(n, n)`` or ``(B, n, n)`` tensors: ``ux
 reference implements (its ``advect_general`` raises otherwise).
 
 Every stage runs on the HIP kernels of ``csrc/tcfd_fvm.hip`` (C ABI ``tcfd_fvm_*``); the pressure solve uses the
-project's own rfft2 / irfft2 kernels.  Forward only: a tableau whose parameters require grad raises while grad mode is on.
+project's own rfft2 / irfft2 kernels.  Gradients with respect to the velocity flow through ``forward`` / ``advance`` (any
+``steps``), ``RKStepper.forward``, ``explicit_terms``, ``pressure_projection``, ``PressureProjection`` and
+``get_trajectory_fvm`` when grad mode is on and ``ux`` or ``uy`` requires grad: ``fvm_autograd.py`` runs the HIP adjoint
+kernels.  A stepping call under grad keeps the input of each of its K steps, ``K * 2 * B * n^2 * w`` bytes (``w`` = 8 for
+fp64, 4 for fp32), until its backward has run.  A tableau whose parameters require grad raises while grad mode is on.
 """
 from __future__ import annotations
 
@@ -21,6 +25,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from . import fvm_autograd as _ad
 from .grids import Grid
 
 _FP = {torch.float64: _lib.TCFD_C128, torch.float32: _lib.TCFD_C64}
@@ -68,7 +73,8 @@ class RKStepper(nn.Module):
     The parameters are stored as the reference stores them -- ``params.a.{i}`` (row i = stage i + 1), ``params.b`` --
     in ``dtype``, float32 by default.  The stage weights are formed as the reference forms them, ``dt * a_ij`` in the
     parameters' precision: an fp64 run of classic RK4 steps with ``b = float32(1/6)``, as there.  Zero entries are
-    skipped."""
+    skipped.  The parameters require grad only with ``requires_grad=True``; gradients with respect to them are not
+    implemented (the step raises in grad mode), those with respect to the velocity are."""
 
     _METHOD_MAP = {
         "forward_euler": {"a": [], "b": [1.0]},
@@ -120,8 +126,8 @@ class RKStepper(nn.Module):
         self.params = nn.ParameterDict()
         self.params["a"] = nn.ParameterList()
         for row in a:
-            self.params["a"].append(nn.Parameter(torch.tensor(row, dtype=self.dtype, requires_grad=self.requires_grad)))
-        self.params["b"] = nn.Parameter(torch.tensor(b, dtype=self.dtype, requires_grad=self.requires_grad))
+            self.params["a"].append(nn.Parameter(torch.tensor(row, dtype=self.dtype), requires_grad=self.requires_grad))
+        self.params["b"] = nn.Parameter(torch.tensor(b, dtype=self.dtype), requires_grad=self.requires_grad)
 
     @classmethod
     def from_method(cls, method: str = "forward_euler", requires_grad: bool = False, **kwargs):
@@ -129,8 +135,9 @@ class RKStepper(nn.Module):
 
     def _check_no_grad(self) -> None:
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise NotImplementedError("RKStepper: the finite-volume step is forward only; its tableau parameters require "
-                                      "grad. Run under torch.no_grad() or build the stepper with requires_grad=False.")
+            raise NotImplementedError("RKStepper: the finite-volume step has no gradients with respect to its tableau, whose "
+                                      "parameters require grad. Run under torch.no_grad() or build the stepper with "
+                                      "requires_grad=False (gradients with respect to the velocity are supported).")
 
     def weights(self, dt: float) -> Tuple[List[float], List[float]]:
         """(a, b) as the kernels take them: ``a`` row-major (stages x stages, row i = stage i) and ``b``, each entry
@@ -178,8 +185,10 @@ class _FvmPlan:
         self._ws: Optional[torch.Tensor] = None
         self._finalizer = weakref.finalize(self, self.lib.tcfd_fvm_plan_destroy, handle)
 
-    def workspace(self, batch: int) -> torch.Tensor:
-        need = self.lib.tcfd_fvm_workspace_bytes(self.handle, batch)
+    def workspace(self, batch: int, need: Optional[int] = None) -> torch.Tensor:
+        """At least ``need`` bytes (default: what ``tcfd_fvm_step`` needs for ``batch``)."""
+        if need is None:
+            need = self.lib.tcfd_fvm_workspace_bytes(self.handle, batch)
         if self._ws is None or self._ws.numel() < need:
             self._ws = None
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
@@ -225,6 +234,54 @@ class _FvmPlan:
                                         int(steps), len(b), _lib.darray(a) if len(a) else None, _lib.darray(b), float(dt),
                                         ws.data_ptr(), ws.numel(), self._stream())
         _lib.check(rc, "tcfd_fvm_step")
+        return ox, oy
+
+    # ---- reverse mode (fvm_autograd.py)
+    def explicit_terms_vjp(self, ux, uy, gx, gy, dt: float):
+        ux, uy, batch = self._prep(ux, uy)
+        gx, gy, _ = self._prep(gx, gy)
+        ox, oy = torch.empty_like(ux), torch.empty_like(uy)
+        with torch.cuda.device(self.device):
+            rc = self.lib.tcfd_fvm_explicit_terms_vjp(self.handle, ux.data_ptr(), uy.data_ptr(), gx.data_ptr(), gy.data_ptr(),
+                                                      ox.data_ptr(), oy.data_ptr(), batch, float(dt), self._stream())
+        _lib.check(rc, "tcfd_fvm_explicit_terms_vjp")
+        return ox, oy
+
+    def step_saving(self, ux, uy, dt: float, a: Sequence[float], b: Sequence[float], steps: int):
+        """``step`` as ``steps`` one-step calls (bit-equal to one call of ``steps``), keeping the input of each:
+        returns ``(saved, ux_out, uy_out)`` with ``saved`` of shape ``(steps, 2, *ux.shape)``."""
+        ux, uy, batch = self._prep(ux, uy)
+        saved = torch.empty((steps, 2) + tuple(ux.shape), dtype=ux.dtype, device=ux.device)
+        ox, oy = torch.empty_like(ux), torch.empty_like(uy)
+        if steps == 0:
+            ox.copy_(ux)
+            oy.copy_(uy)
+            return saved, ox, oy
+        saved[0, 0].copy_(ux)
+        saved[0, 1].copy_(uy)
+        ws = self.workspace(batch)
+        ca, cb = (_lib.darray(a) if len(a) else None), _lib.darray(b)
+        with torch.cuda.device(self.device):
+            for s in range(steps):
+                tx, ty = (saved[s + 1, 0], saved[s + 1, 1]) if s + 1 < steps else (ox, oy)
+                rc = self.lib.tcfd_fvm_step(self.handle, saved[s, 0].data_ptr(), saved[s, 1].data_ptr(), tx.data_ptr(),
+                                            ty.data_ptr(), batch, 1, len(b), ca, cb, float(dt), ws.data_ptr(), ws.numel(),
+                                            self._stream())
+                _lib.check(rc, "tcfd_fvm_step")
+        return saved, ox, oy
+
+    def step_vjp(self, saved, gx, gy, dt: float, a: Sequence[float], b: Sequence[float]):
+        """Cotangent of the input of ``step_saving``'s steps from that of their result (``saved``: its record)."""
+        gx, gy, batch = self._prep(gx, gy)
+        ox, oy = torch.empty_like(gx), torch.empty_like(gy)
+        steps = saved.shape[0]
+        ws = self.workspace(batch, self.lib.tcfd_fvm_step_vjp_workspace_bytes(self.handle, batch))
+        with torch.cuda.device(self.device):
+            rc = self.lib.tcfd_fvm_step_vjp(self.handle, saved.data_ptr() if steps else None, gx.data_ptr(), gy.data_ptr(),
+                                            ox.data_ptr(), oy.data_ptr(), batch, int(steps), len(b),
+                                            _lib.darray(a) if len(a) else None, _lib.darray(b), float(dt), ws.data_ptr(),
+                                            ws.numel(), self._stream())
+        _lib.check(rc, "tcfd_fvm_step_vjp")
         return ox, oy
 
 
@@ -301,7 +358,10 @@ class PressureProjection(nn.Module):
 
     def forward(self, v):
         ux, uy = _as_pair(v)
-        return self._plan(ux.dtype, ux.device).project(ux, uy)
+        plan = self._plan(ux.dtype, ux.device)
+        if _ad.wants_grad(ux, uy):
+            return _ad.ProjectFn.apply(plan, ux, uy)
+        return plan.project(ux, uy)
 
 
 # ----------------------------------------------------------------------------- the equation
@@ -311,7 +371,9 @@ class NavierStokes2DFVMProjection(nn.Module):
     projected onto discretely divergence-free fields (torch_cfd/fvm.py:334).
 
     ``forward(u, dt, steps=1)`` runs ``steps`` steps of ``solver`` (an ``RKStepper``) in one device call and returns the
-    pair ``(ux, uy)``; ``explicit_terms(u, dt)`` and ``pressure_projection(u)`` are the two halves on their own."""
+    pair ``(ux, uy)``; ``explicit_terms(u, dt)`` and ``pressure_projection(u)`` are the two halves on their own.  All three
+    are differentiable with respect to ``u`` (``fvm_autograd.py``); under grad, ``forward`` runs one device call per step
+    and keeps each step's input, ``steps * 2 * B * n^2 * w`` bytes, for its backward."""
 
     def __init__(self, viscosity: float, grid: Grid, bcs=None, drag: float = 0.0, density: float = 1.0, forcing=None,
                  solver: Optional[RKStepper] = None, **kwargs):
@@ -350,7 +412,10 @@ class NavierStokes2DFVMProjection(nn.Module):
 
     def explicit_terms(self, u, dt: float):
         ux, uy = _as_pair(u)
-        return self._plan(ux.dtype, ux.device).explicit_terms(ux, uy, dt)
+        plan = self._plan(ux.dtype, ux.device)
+        if _ad.wants_grad(ux, uy):
+            return _ad.ExplicitTermsFn.apply(plan, dt, ux, uy)
+        return plan.explicit_terms(ux, uy, dt)
 
     def pressure_projection(self, u):
         return self._projection(u)
@@ -362,7 +427,10 @@ class NavierStokes2DFVMProjection(nn.Module):
         solver._check_no_grad()
         ux, uy = _as_pair(u)
         a, b = solver.weights(dt)
-        return self._plan(ux.dtype, ux.device).step(ux, uy, dt, a, b, steps)
+        plan = self._plan(ux.dtype, ux.device)
+        if _ad.wants_grad(ux, uy):
+            return _ad.StepFn.apply(plan, dt, a, b, steps, ux, uy)
+        return plan.step(ux, uy, dt, a, b, steps)
 
     def forward(self, u, dt: float, steps: int = 1):
         return self.advance(u, dt, steps=steps)
@@ -371,7 +439,7 @@ class NavierStokes2DFVMProjection(nn.Module):
 def get_trajectory_fvm(equation: NavierStokes2DFVMProjection, u0, dt: float, num_steps: int, record_every_steps: int):
     """Run ``num_steps`` steps from ``u0`` and record the state after every ``record_every_steps`` of them: returns
     ``(ux, uy)`` stacked over the records on the dimension before the grid ((T, n, n), or (B, T, n, n) for a batch).
-    The notebook's inner / outer loop without a host synchronisation per step."""
+    The notebook's inner / outer loop without a host synchronisation per step; differentiable with respect to ``u0``."""
     if record_every_steps <= 0 or num_steps % record_every_steps:
         raise ValueError(f"num_steps = {num_steps} is not a positive multiple of record_every_steps = {record_every_steps}")
     u = _as_pair(u0)
