@@ -56,7 +56,7 @@ typedef struct tcfd_ns2d_plan tcfd_ns2d_plan;
 typedef struct tcfd_fno_plan tcfd_fno_plan;
 typedef struct tcfd_fvm_plan tcfd_fvm_plan;
 
-#define TCFD_ABI_VERSION 9   /* what tcfd_version() of a library built from THIS header returns */
+#define TCFD_ABI_VERSION 10  /* what tcfd_version() of a library built from THIS header returns */
 
 #ifndef TCFD_H_TYPES_ONLY   /* (the library's second compilation unit wants the types without the prototypes) */
 
@@ -65,7 +65,8 @@ const char* tcfd_last_error(void);
  * meaning of an argument (round 3 turned the float scalars of the tcfd_fno_* calls into doubles and gave tcfd_fno_contract
  * a dtype: revision 1 -> 4; round 5: 6, tcfd_fno_pointwise_pre / _bwd_saved / _profile_*, tcfd_fno_spectral_conv_pointwise
  * removed; 7: tcfd_sobolev_loss_backward, tcfd_fno_forward_trunc_kt / _inverse_trunc_kt added -- a host written against 7 needs them;
- * 8: tcfd_fvm_*; 9: tcfd_fvm_explicit_terms_vjp, tcfd_fvm_step_vjp_workspace_bytes, tcfd_fvm_step_vjp).  A host compares it with the TCFD_ABI_VERSION it was written against BEFORE the
+ * 8: tcfd_fvm_*; 9: tcfd_fvm_explicit_terms_vjp, tcfd_fvm_step_vjp_workspace_bytes, tcfd_fvm_step_vjp; 10: tcfd_ns2d_refine,
+ * tcfd_ns2d_refine_vjp, tcfd_ns2d_refine_workspace_bytes).  A host compares it with the TCFD_ABI_VERSION it was written against BEFORE the
  * first call: a stale prebuilt library would otherwise be called with the wrong argument layout and return garbage
  * (torch-cfd_amd/_lib.py::load does). */
 int tcfd_version(void);
@@ -155,6 +156,24 @@ int tcfd_ns2d_explicit_terms_vjp(const tcfd_ns2d_plan* plan, const void* w, cons
 /* wbar (batch, plane) = sum_f post_f (.) X_f: the closing sum of the vector-Jacobian product above (X = xout, post (4, plane)
  * complex tables -(c / n^2) conj(a_f) built by the caller) in one pass. */
 int tcfd_ns2d_vjp_combine(const void* X, const void* post, void* out, long batch, long plane, int dtype, void* stream);
+
+/* Spectral refiner (fno/finetune.py::OutConvFT._fine_tune) on a plan whose linear term is the Laplacian table (L(0,0) = 1),
+ * whose mask is the de-aliasing filter (all ones without de-aliasing) and which has no forcing.  w: real time-last
+ * trajectories (batch, n, n, nt) in the plan's precision; f_hat: NULL or a forcing half spectrum (batch, n, m) shared by the
+ * nt steps of a sample.  Per step, with C(.) = mask . rfft2(u.grad(.)):
+ *     wh = rfft2(w), wn(d) = (-d C(wh) + d f + (1 + d nu L / 2) wh) / (1 - d nu L / 2), wt(d) = (wn(d) - wh) / d,
+ *     W = bdf0 wn(-dt) + bdf1 wn(dt), Wt = bdf0 wt(-dt) + bdf1 wt(dt), R = Wt + C(W) - nu L W - f
+ * and w_out, wt_out, res_out (each NULL or real time-last like w) receive irfft2 of W, Wt, R.
+ * refine_vjp: the cotangents g_w, g_wt, g_res of the three outputs (each may be NULL = zero) -> grad_w (time-last, like w)
+ * and, when grad_f_hat is not NULL, the cotangent of f_hat (batch, n, m).  Workspace of both:
+ * tcfd_ns2d_refine_workspace_bytes(plan, batch, nt). */
+size_t tcfd_ns2d_refine_workspace_bytes(const tcfd_ns2d_plan* plan, long batch, int nt);
+int tcfd_ns2d_refine(const tcfd_ns2d_plan* plan, const void* w, const void* f_hat, void* w_out, void* wt_out, void* res_out,
+                     long batch, int nt, double dt, double visc, double bdf0, double bdf1, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int tcfd_ns2d_refine_vjp(const tcfd_ns2d_plan* plan, const void* w, const void* f_hat, const void* g_w, const void* g_wt,
+                         const void* g_res, void* grad_w, void* grad_f_hat, long batch, int nt, double dt, double visc,
+                         double bdf0, double bdf1, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Stage bookkeeping of the differentiable step with constant coefficients (what autograd derives for the low-storage RK /
  * Crank-Nicolson stage of torch_cfd/equations.py:139-160, 355-357 when only the STATE requires grad), one launch each way:

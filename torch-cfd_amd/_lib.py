@@ -27,7 +27,7 @@ LIB_PATH = os.path.join(CSRC, LIB_NAME)
 SOURCES = ("tcfd_ns2d.hip", "tcfd_fno.hip", "tcfd_fno_pw.hip", "tcfd_fno_tiles.hip", "tcfd_loss.hip", "tcfd_fvm.hip")
 
 TCFD_C64, TCFD_C128 = 0, 1
-ABI_VERSION = 9   # TCFD_ABI_VERSION of include/tcfd.h the SIGNATURES table below was written against
+ABI_VERSION = 10  # TCFD_ABI_VERSION of include/tcfd.h the SIGNATURES table below was written against
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -127,6 +127,9 @@ SIGNATURES = {
     "tcfd_ns2d_vjp_combine": (_i, [_vp, _vp, _vp, _l, _l, _i, _vp]),
     "tcfd_ns2d_stage_update": (_i, [_vp, _vp, _vp, _vp, ctypes.POINTER(_d), _vp, _vp, _l, _l, _i, _vp]),
     "tcfd_ns2d_stage_update_vjp": (_i, [_vp, _vp, _vp, ctypes.POINTER(_d), _vp, _vp, _vp, _l, _l, _i, _vp]),
+    "tcfd_ns2d_refine_workspace_bytes": (_sz, [_vp, _l, _i]),
+    "tcfd_ns2d_refine": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _d, _d, _d, _d, _vp, _sz, _vp]),
+    "tcfd_ns2d_refine_vjp": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _d, _d, _d, _d, _vp, _sz, _vp]),
     "tcfd_ns2d_stream_residual": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _vp, _sz, _vp]),
     "tcfd_ns2d_velocity": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "tcfd_rfft2": (_i, [_vp, _vp, _vp, _l, _vp]),

@@ -1251,6 +1251,14 @@ class SpectralConv(nn.Module):
     def _bias_list(self):
         return list(self.bias) if isinstance(self.bias, nn.ParameterList) else None
 
+    def _reset_parameters(self, gain=1e-6):
+        """Zero biases, Xavier-uniform weights with ``gain`` (fno/base.py:169-174; the fine-tuning head's fresh layer)."""
+        for name, param in self.named_parameters():
+            if "bias" in name:
+                nn.init.constant_(param, 0.0)
+            else:
+                nn.init.xavier_uniform_(param, gain)
+
     # -- the dimension-generic template of fno/base.py:114-237: 2 (dim - 1) weight blocks, a channel contraction over any
     #    number of mesh axes, forward = rfftn -> spectral_conv (the subclass's) -> irfftn.  The (2+1)-D subclasses below
     #    replace ``forward`` by the fused HIP kernels; any other dimension runs the two transforms as dense matrix products
@@ -1819,6 +1827,25 @@ class FNOBase(nn.Module):
         self.debug = debug
         self.num_spectral_layers = num_spectral_layers
 
+    # forward-hook outputs by layer name (fno/base.py:328-343).  A CLASS attribute, as in the reference: every model shares it.
+    latent_tensors = {}
+
+    def add_latent_hook(self, layer_name: str):
+        """Record the (detached) output of ``layer_name`` -- each member of a module list as ``{layer_name}_{k}`` -- in
+        ``latent_tensors`` on every forward.  The fine-tuning workflow takes the latent of the output head from here."""
+        def _get_latent_tensors(name):
+            def hook(model, input, output):
+                self.latent_tensors[name] = output.detach()
+
+            return hook
+
+        module = getattr(self, layer_name)
+        if hasattr(module, "__iter__"):
+            for k, b in enumerate(module):
+                b.register_forward_hook(_get_latent_tensors(f"{layer_name}_{k}"))
+        else:
+            module.register_forward_hook(_get_latent_tensors(layer_name))
+
     def double(self):
         """Parameters to float64 / complex128 (fno/base.py:342-349).  An fp64 model runs the SAME fused kernels as an
         fp32 one, instantiated for double (transforms, contraction on v_mfma_f64_16x16x4_f64, pointwise block)."""
@@ -1875,10 +1902,15 @@ class SFNO(FNOBase):
             x1 = conv(v)
             fused = hip_pointwise(x1, mlp.linear1, mlp.activation, mlp.linear2, skip=v, skip_conv=w, act2=act)
             v = fused if fused is not None else act(mlp(x1) + w(v))
-        out = self.output_operator.fused_forward(v, v_res, self.reduction, out_steps) if type(self.output_operator) is OutConv else None
+        hooked = bool(self.reduction._forward_hooks)     # add_latent_hook("reduction"): the latent must pass through here
+        out = (self.output_operator.fused_forward(v, v_res, self.reduction, out_steps)
+               if type(self.output_operator) is OutConv and not hooked else None)
         if out is not None:
             return out
         red = hip_pointwise(v, None, None, self.reduction)
+        if red is not None and hooked:
+            for hook in list(self.reduction._forward_hooks.values()):   # the fused kernel bypasses the module's __call__
+                hook(self.reduction, (v,), red)
         v = red if red is not None else self.reduction(v)
         return self.output_operator(v, v_res, out_steps=out_steps)
 

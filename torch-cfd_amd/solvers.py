@@ -13,6 +13,8 @@ on the device side:
 from __future__ import annotations
 
 import math
+import weakref
+from collections import OrderedDict
 from datetime import datetime
 from typing import Callable, Dict, Optional
 
@@ -95,25 +97,65 @@ def get_trajectory_imex(
 
 
 # ----------------------------------------------------------------------------- legacy IMEX Crank-Nicolson step
-_CN_PLANS: Dict[tuple, object] = {}
+_CN_PLANS: Dict[tuple, object] = {}      # by table VALUES: plans are shared by equal tables
+_CN_BOUND: "OrderedDict[tuple, tuple]" = OrderedDict()   # by table IDENTITY (+ _version): no host copy on a hit
+_CN_BOUND_MAX = 16
 
 
-def _convection_hat(w: torch.Tensor, kx: torch.Tensor, ky: torch.Tensor, mask: torch.Tensor):
-    """rfft2(u w_x + v w_y) (times ``mask``) = minus the de-aliased advection term of the RK operator: the same
-    three HIP kernels (column pass, fused row pass, column pass) with a plan that has no linear term / forcing."""
+def _ident(t):
+    return None if t is None else (id(t), t.data_ptr(), t._version)
+
+
+def _cn_bind(w: torch.Tensor, kx: torch.Tensor, ky: torch.Tensor, mask_src):
+    """(plan, op) for the convection of w under the tables (kx, ky, mask_src; mask_src None = no de-aliasing).  Resolved by
+    the tables' identity and ``_version``: a call with the same table tensors as an earlier one copies nothing to the host
+    (the tables are read back, once, only when new tensors appear)."""
+    from types import SimpleNamespace
+
     from .equations import _COMPLEX_OF, _HipPlan
 
     n, m = w.shape[-2:]
     cdtype = torch.promote_types(w.dtype, _COMPLEX_OF.get(kx.dtype, torch.complex64))
+    key = (n, cdtype, w.device, _ident(kx), _ident(ky), _ident(mask_src))
+    hit = _CN_BOUND.get(key)
+    if hit is not None and all(r() is t for r, t in zip(hit[0], (kx, ky, mask_src)) if t is not None):
+        _CN_BOUND.move_to_end(key)
+        return hit[1], hit[2]
     kx1 = kx.reshape(-1, n, m)[0, :, 0].detach().cpu().double()
     ky1 = ky.reshape(-1, n, m)[0, 0, :].detach().cpu().double()
-    mk = mask.reshape(-1, n, m)[0].detach().cpu().double()
-    key = (n, cdtype, w.device, float(kx1[1]), float(ky1[1]), float(mk.sum()), int(mk[:, 0].sum()), int(mk[0, :].sum()))
-    plan = _CN_PLANS.get(key)
+    mk = (mask_src.reshape(-1, n, m)[0].detach().cpu().double() if mask_src is not None
+          else torch.ones(n, m, dtype=torch.float64))
+    vkey = (n, cdtype, w.device, float(kx1[1]), float(ky1[1]), float(mk.sum()), int(mk[:, 0].sum()), int(mk[0, :].sum()))
+    plan = _CN_PLANS.get(vkey)
     if plan is None:
         plan = _HipPlan(n, cdtype, w.device, kx1, ky1, torch.zeros(n, m), mk)
-        _CN_PLANS[key] = plan
-    return -plan.explicit_terms(w).reshape(w.shape)
+        _CN_PLANS[vkey] = plan
+    real = plan.rdtype
+    kx2 = kx.reshape(-1, n, m)[0].detach().to(device=w.device, dtype=real)
+    ky2 = ky.reshape(-1, n, m)[0].detach().to(device=w.device, dtype=real)
+    filt = (mask_src.reshape(-1, n, m)[0].detach().to(device=w.device, dtype=real) if mask_src is not None
+            else torch.ones_like(kx2))
+    op = SimpleNamespace(kx=kx2, ky=ky2, filter=filt, smooth=mask_src is not None)
+    refs = tuple(weakref.ref(t) if t is not None else None for t in (kx, ky, mask_src))
+    _CN_BOUND[key] = (refs, plan, op)
+    while len(_CN_BOUND) > _CN_BOUND_MAX:
+        _CN_BOUND.popitem(last=False)
+    return plan, op
+
+
+def _convection_hat(w: torch.Tensor, kx: torch.Tensor, ky: torch.Tensor, mask_src=None):
+    """rfft2(u w_x + v w_y) (times the mask ``mask_src``, None: no mask) = minus the de-aliased advection term of the RK
+    operator: the same three HIP kernels (column pass, fused row pass, column pass) with a plan that has no linear term /
+    forcing.  Differentiable in w: under grad it is ``FusedExplicitTerms`` (the fused VJP kernels), so the convection
+    Jacobian reaches the gradients of ``imex_crank_nicolson_step`` and ``update_residual``."""
+    from .autograd import explicit_terms
+
+    plan, op = _cn_bind(w, kx, ky, mask_src)
+    shape = w.shape
+    w3 = w.reshape(-1, plan.n, plan.m)
+    if w3.dtype != plan.cdtype:
+        w3 = w3.to(plan.cdtype)
+    return -explicit_terms(op, plan, w3, None).reshape(shape)
 
 
 def _cn_tables(w, diam, rfftmesh, laplacian, dealias_filter):
@@ -139,8 +181,7 @@ def update_residual(w_h, w_h_t, f_h, visc, rfftmesh, laplacian, dealias_filter=N
     """Residual  w_t + u.grad(w) - nu lap w - f  in Fourier space (fno/data_gen/solvers.py:49-88)."""
     kx, ky = rfftmesh
     use = dealias and dealias_filter is not None
-    mask = dealias_filter.to(kx.dtype) if use else torch.ones_like(kx)
-    conv = _convection_hat(w_h, kx, ky, mask)
+    conv = _convection_hat(w_h, kx, ky, dealias_filter if use else None)
     return w_h_t + conv - visc * laplacian * w_h - f_h
 
 
@@ -156,8 +197,7 @@ def imex_crank_nicolson_step(w, f, visc, delta_t, diam: float = 1, rfftmesh=None
         f = f.unsqueeze(0)
     f = f.to(w.device)
     psi_h = -w / laplacian
-    mask = dealias_filter.to(kx.dtype) if dealias else torch.ones_like(kx)
-    convection_h = _convection_hat(w, kx, ky, mask)
+    convection_h = _convection_hat(w, kx, ky, dealias_filter if dealias else None)
     half = 0.5 * delta_t * visc * laplacian
     w_next = (-delta_t * convection_h + delta_t * f + (1.0 + half) * w) / (1.0 - half)
     dwdt = (w_next - w) / delta_t
