@@ -24,7 +24,7 @@ CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_NAME = "libtcfd_hip.so"
 LIB_PATH = os.path.join(CSRC, LIB_NAME)
-SOURCES = ("tcfd_ns2d.hip", "tcfd_fno.hip", "tcfd_fno_pw.hip", "tcfd_fno_tiles.hip", "tcfd_loss.hip", "tcfd_fvm.hip")
+SOURCES = ("tcfd_ns2d.hip", "tcfd_fno.hip", "tcfd_fno_pw.hip", "tcfd_fno_tiles.hip", "tcfd_fno3d.hip", "tcfd_loss.hip", "tcfd_fvm.hip")
 
 TCFD_C64, TCFD_C128 = 0, 1
 ABI_VERSION = 10  # TCFD_ABI_VERSION of include/tcfd.h the SIGNATURES table below was written against
@@ -69,14 +69,17 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
 
 
 # compile jobs: (source, extra flags, object).  tcfd_ns2d.hip is compiled twice -- unit 0 = C ABI + float64 kernels, unit 1 =
-# float32 kernels -- and the FNO kernels are three files (transforms + contraction / pointwise block / tiled backward), so that
+# float32 kernels -- and the FNO kernels are three files (transforms + contraction / pointwise block / tiled backward; the tiled
+# backward twice: unit 0 = the SFNO's blocks, unit 1 = the FNO3d baseline's), so that
 # the hipcc processes take ~3.5 minutes side by side instead of 7 + 5 one after the other.  tcfd_fvm.hip (finite-volume solver) is
 # compiled twice the same way: unit 0 = C ABI + float64 kernels, unit 1 = float32 kernels.
 JOBS = (("tcfd_ns2d.hip", ("-DTCFD_UNIT=0",), "tcfd_ns2d.o"),
         ("tcfd_ns2d.hip", ("-DTCFD_UNIT=1",), "tcfd_ns2d_f32.o"),
         ("tcfd_fno.hip", (), "tcfd_fno.o"),
         ("tcfd_fno_pw.hip", (), "tcfd_fno_pw.o"),
-        ("tcfd_fno_tiles.hip", (), "tcfd_fno_tiles.o"),
+        ("tcfd_fno_tiles.hip", ("-DTCFD_TILES_UNIT=0",), "tcfd_fno_tiles.o"),
+        ("tcfd_fno_tiles.hip", ("-DTCFD_TILES_UNIT=1",), "tcfd_fno_tiles_fno3d.o"),
+        ("tcfd_fno3d.hip", (), "tcfd_fno3d.o"),
         ("tcfd_loss.hip", (), "tcfd_loss.o"),
         ("tcfd_fvm.hip", ("-DTCFD_UNIT=0",), "tcfd_fvm.o"),
         ("tcfd_fvm.hip", ("-DTCFD_UNIT=1",), "tcfd_fvm_f32.o"))

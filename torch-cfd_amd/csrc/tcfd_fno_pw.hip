@@ -190,6 +190,11 @@ static int pw_dispatch(PwArgs a, int batch, int ci, int cm, int co, hipStream_t 
     }
 #undef PW_CASE
 #undef PW_ANY
+    {   // the rectangular members of the family (tcfd_fno3d.hip): single layer ci -> W, head W -> E -> 1
+        int handled = 0;
+        const int rc = tcfd_pw_fno3d_dispatch(a, batch, ci, cm, co, st, &handled);
+        if (handled) return rc;
+    }
     return FAIL(TCFD_EINVAL, "fno_pointwise: channels (%d -> %d -> %d) not instantiated", ci, cm, co);
 }
 
@@ -784,6 +789,11 @@ static int pointwise_bwd_impl(const void* pe, const void* x, const void* skip, c
     PWB_CASE(20, 20, 20, false) PWB_CASE(20, 20, 1, false) PWB_CASE(24, 24, 24, false) PWB_CASE(24, 24, 1, false)
     PWB_CASE(32, 32, 32, false) PWB_CASE(32, 32, 1, false)
 #undef PWB_CASE
+    if (!l1) {   // the rectangular single layer ci -> W (tcfd_fno3d.hip)
+        int handled = 0;
+        const int rc = tcfd_pwb_rect_dispatch(a, batch, ci, co, max_waves, dims, st, &handled);
+        if (handled) return rc;
+    }
     return FAIL(TCFD_EINVAL, "fno_pointwise_bwd: channels (%d -> %d -> %d) not instantiated", ci, cm, co);
 }
 

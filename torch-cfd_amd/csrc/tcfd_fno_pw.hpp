@@ -260,5 +260,13 @@ __device__ __forceinline__ void pw_skip_conv(const PwArgs& a, const vf (&sv)[CI]
 // call (or answered the layout query), leaves *handled = 0 for combinations it does not cover.
 int tcfd_pwb_tiles_dispatch(const PwBwdArgs& a, int batch, int ci, int cm, int co, int max_rows, int* dims, hipStream_t st,
                             int* handled);
+// tcfd_fno_tiles.hip, compile unit 1: the same kernel for the blocks of the FNO3d baseline (layer tail W -> W -> W, head W -> E -> 1);
+// tcfd_pwb_tiles_dispatch ends in it
+int tcfd_pwb_tiles_dispatch_fno3d(const PwBwdArgs& a, int batch, int ci, int cm, int co, int max_rows, int* dims, hipStream_t st,
+                                  int* handled);
 // tcfd_fno_tiles.hip: the forward block of the wide layers on the matrix pipe (same contract: *handled = 0 -> not covered)
 int tcfd_pwf_tiles_dispatch(const PwArgs& a, int batch, int ci, int cm, int co, hipStream_t st, int* handled);
+// tcfd_fno3d.hip: the rectangular members of the family (FNO3d baseline) -- forward of the single layer ci -> W and of the head
+// W -> E -> 1; backward of the single layer ci -> W.  Same contract: *handled = 0 -> not covered.
+int tcfd_pw_fno3d_dispatch(const PwArgs& a, int batch, int ci, int cm, int co, hipStream_t st, int* handled);
+int tcfd_pwb_rect_dispatch(const PwBwdArgs& a, int batch, int ci, int co, int max_waves, int* dims, hipStream_t st, int* handled);

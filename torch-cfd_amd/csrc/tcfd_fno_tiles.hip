@@ -740,14 +740,18 @@ int launch_tiles_act(const PwBwdArgs& a, int batch, int max_rows, int* dims, hip
     return launch_tiles<CI, CM, CO, MODE, -1, WPS>(a, batch, max_rows, dims, st);
 }
 
-template <int CI, int CM, int CO, int WPS>
-int launch_tiles_mode(const PwBwdArgs& a, int batch, int max_rows, int* dims, hipStream_t st) {
+// MODES: bit k set = skip_mode k is instantiated (the SFNO blocks: all three; the FNO3d layer tail: none / skip convolution; the
+// FNO3d head: none) -- a mode that is not leaves *handled = 0 and the caller answers "not instantiated"
+template <int CI, int CM, int CO, int WPS, int MODES = 7>
+int launch_tiles_mode(const PwBwdArgs& a, int batch, int max_rows, int* dims, hipStream_t st, int* handled) {
     using Lay = PwBwdGeom<CI, CM, CO, true>;
+    if (!((MODES >> a.skip_mode) & 1)) return 0;
+    *handled = 1;
     dims[0] = Lay::COP; dims[1] = Lay::CB; dims[2] = Lay::CM1; dims[3] = Lay::CIP; dims[4] = Lay::TOTAL; dims[5] = 0;
     if (!a.x) {                                               // layout query: dims[5] = rows a launch that fills the device writes
         int dev = 0, cus = 256, per_cu = 0;
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) {
-            auto kern = k_pwb_tiles<CI, CM, CO, 1, 1, WPS>;   // (every MODE / ACT variant of a width has the same WPS and LDS)
+            auto kern = k_pwb_tiles<CI, CM, CO, (MODES & 2) ? 1 : 0, (MODES & 2) ? 1 : -1, WPS>;   // (every MODE / ACT variant of a width has the same WPS and LDS)
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TilesGeom<CI, CM, CO>::LDS);
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 256, TilesGeom<CI, CM, CO>::LDS) == hipSuccess)
                 dims[5] = std::max(per_cu, 1) * cus * 4;
@@ -755,8 +759,8 @@ int launch_tiles_mode(const PwBwdArgs& a, int batch, int max_rows, int* dims, hi
         (void)hipGetLastError();
         return 0;
     }
-    if (a.skip_mode == 1) return launch_tiles_act<CI, CM, CO, 1, WPS>(a, batch, max_rows, dims, st);
-    if (a.skip_mode == 2) return launch_tiles_act<CI, CM, CO, 2, WPS>(a, batch, max_rows, dims, st);
+    if constexpr ((MODES & 2) != 0) if (a.skip_mode == 1) return launch_tiles_act<CI, CM, CO, 1, WPS>(a, batch, max_rows, dims, st);
+    if constexpr ((MODES & 4) != 0) if (a.skip_mode == 2) return launch_tiles_act<CI, CM, CO, 2, WPS>(a, batch, max_rows, dims, st);
     return launch_tiles<CI, CM, CO, 0, -1, WPS>(a, batch, max_rows, dims, st);
 }
 
@@ -1045,6 +1049,7 @@ int launch_fwd_tiles_mode(const PwArgs& a, int batch, hipStream_t st) {
 
 }  // namespace
 
+#if !defined(TCFD_TILES_UNIT) || TCFD_TILES_UNIT != 1
 // The widths the reference's own code uses (10: fno/train.py:293; 16: fno/sfno_pytest.py:261; 20: its notebooks) and the
 // even widths around them (4 ... 16, 24, 32), with its channel expansion of 4 (fno/sfno.py:479).  The kernel needs the block's saved output /
 // pre-activation unless the output activation is the identity.
@@ -1054,16 +1059,47 @@ int tcfd_pwb_tiles_dispatch(const PwBwdArgs& a, int batch, int ci, int cm, int c
     if (a.pe || a.per_sample || a.P % 4 != 0) return 0;                                      // (known at the layout query too)
     if (a.x && (max_rows < 4 || !a.w1 || (a.act2 != 0 && !a.out))) return 0;
 #define PWT_CASE(CI_, CM_, CO_, WPS_)                                                          \
-    if (ci == CI_ && cm == CM_ && co == CO_) {                                                  \
-        *handled = 1;                                                                           \
-        return launch_tiles_mode<CI_, CM_, CO_, WPS_>(a, batch, max_rows, dims, st);            \
-    }
+    if (ci == CI_ && cm == CM_ && co == CO_)                                                    \
+        return launch_tiles_mode<CI_, CM_, CO_, WPS_>(a, batch, max_rows, dims, st, handled);
     PWT_CASE(4, 16, 4, 2) PWT_CASE(6, 24, 6, 2) PWT_CASE(8, 32, 8, 2) PWT_CASE(10, 40, 10, 2) PWT_CASE(12, 48, 12, 2)
     PWT_CASE(14, 56, 14, 2) PWT_CASE(16, 64, 16, 2) PWT_CASE(20, 80, 20, 1) PWT_CASE(24, 96, 24, 1) PWT_CASE(32, 128, 32, 1)
 #undef PWT_CASE
+    return tcfd_pwb_tiles_dispatch_fno3d(a, batch, ci, cm, co, max_rows, dims, st, handled);
+}
+#endif   // TCFD_TILES_UNIT != 1
+
+#if !defined(TCFD_TILES_UNIT) || TCFD_TILES_UNIT == 1
+// The blocks of the FNO3d baseline (fno/fno3d.py:119-236) on the same kernel -- every channel dimension is tiled, nothing in it ties
+// the hidden width to 4 x the width:
+//   * the layer tail  act(mlp2(GELU(mlp1(K v))) + w(v)):  W -> W -> W with the skip convolution (or none), every even width 4 ... 32;
+//   * the head  mlp2(GELU(mlp1(v)))  with last_activation:  W -> E -> 1, E in {32, 64, 128} hidden units as E / 16 hidden tiles, no skip.
+//     The (b, E, P) hidden tensor lives in registers 16 points at a time.  One output channel fills a sixteenth of the products that
+//     have co on a side (dh, dW2: 8 + 32 of the 128 matrix instructions per 16 points at W = 10, E = 128); the E erf-GELUs with their
+//     derivatives take about as long as all the products and do not overlap them (profiles/r03_mfma_f32_vs_valu_overlap.txt), so
+//     the kernel is bound by instruction issue, ~10 x above its HBM time.
+// A compile unit of its own (TCFD_TILES_UNIT=1): these instances would double the build time of the SFNO's.
+int tcfd_pwb_tiles_dispatch_fno3d(const PwBwdArgs& a, int batch, int ci, int cm, int co, int max_rows, int* dims, hipStream_t st,
+                                  int* handled) {
+    *handled = 0;
+#define PWT_TAIL(W_, WPS_)                                                                     \
+    if (ci == W_ && cm == W_ && co == W_)                                                       \
+        return launch_tiles_mode<W_, W_, W_, WPS_, 3>(a, batch, max_rows, dims, st, handled);
+    PWT_TAIL(4, 2) PWT_TAIL(6, 2) PWT_TAIL(8, 2) PWT_TAIL(10, 2) PWT_TAIL(12, 2) PWT_TAIL(14, 2) PWT_TAIL(16, 2) PWT_TAIL(18, 1)
+    PWT_TAIL(20, 1) PWT_TAIL(22, 1) PWT_TAIL(24, 1) PWT_TAIL(26, 1) PWT_TAIL(28, 1) PWT_TAIL(30, 1) PWT_TAIL(32, 1)
+#undef PWT_TAIL
+#define PWT_HEAD(W_, E_)                                                                       \
+    if (ci == W_ && cm == E_ && co == 1)                                                        \
+        return launch_tiles_mode<W_, E_, 1, 1, 1>(a, batch, max_rows, dims, st, handled);
+#define PWT_HEADS(W_) PWT_HEAD(W_, 32) PWT_HEAD(W_, 64) PWT_HEAD(W_, 128)
+    PWT_HEADS(4) PWT_HEADS(6) PWT_HEADS(8) PWT_HEADS(10) PWT_HEADS(12) PWT_HEADS(14) PWT_HEADS(16) PWT_HEADS(20) PWT_HEADS(24)
+    PWT_HEADS(32)
+#undef PWT_HEADS
+#undef PWT_HEAD
     return 0;
 }
+#endif
 
+#if !defined(TCFD_TILES_UNIT) || TCFD_TILES_UNIT != 1
 // Forward block of the wide layers on the matrix pipe (k_pwf_tiles): widths 24 / 32 with cm = 4 ci, shared weights, P % 4 == 0,
 // the (batch, C, P) layout.  Measured at the config-5 grid, per launch (profiles/r05_pw_fwd_tiles_timing.json): width 24 2.61 ms
 // against 3.19 for k_pointwise, width 32 3.75 against 6.60 -- and width 16 1.76 against 1.45, width 20 2.13 against 1.66 (36 / 75
@@ -1086,3 +1122,4 @@ int tcfd_pwf_tiles_dispatch(const PwArgs& a, int batch, int ci, int cm, int co, 
 #undef PWF_CASE
     return 0;
 }
+#endif

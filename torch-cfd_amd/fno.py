@@ -7,6 +7,7 @@ names / shapes and ``state_dict`` keys):
   * ``SpectralConvS``     fno/sfno.py:331-394
   * ``SpectralConvT``     fno/sfno.py:397-457   (time padding / arbitrary output steps)
   * ``SpectralConv3d``    fno/fno3d.py:19-116   (4 complex ``weights1..4`` parameters)
+  * ``MLP``, ``FNO3d``    fno/fno3d.py:119-236  (the baseline model of examples/ex2_FNO3d_train_normalized.ipynb)
   * ``LayerNormnd``, ``PointwiseFFN``, ``SpaceTimePositionalEncoding``, ``HelmholtzProjection``,
     ``LiftingOperator``, ``OutConv``, ``SFNO``   fno/base.py:61-111, fno/sfno.py:25-328, 460-620
 
@@ -875,7 +876,10 @@ def hip_spectral_layer(conv, v, lin1, act1, lin2, skip_conv=None, act2=None, ski
     # a user subclass that overrides forward() / spectral_conv() is a different convolution: it must run under grad exactly
     # as it runs under no_grad (through conv(v)), never be rebuilt from the parent's parameters
     cls = type(conv)
-    if cls.forward not in (SpectralConvS.forward, SpectralConvT.forward) or cls.spectral_conv is not SpectralConvS.spectral_conv \
+    if isinstance(conv, SpectralConv3d):
+        if cls.forward is not SpectralConv3d.forward or cls._plain_args is not SpectralConv3d._plain_args:
+            return None
+    elif cls.forward not in (SpectralConvS.forward, SpectralConvT.forward) or cls.spectral_conv is not SpectralConvS.spectral_conv \
             or cls._plain_args not in (SpectralConvS._plain_args, SpectralConvT._plain_args):
         return None
     cargs = conv._plain_args(v, out_steps)
@@ -1419,9 +1423,164 @@ class SpectralConv3d(nn.Module):
         for k in (1, 2, 3, 4):
             setattr(self, f"weights{k}", nn.Parameter(self.scale * torch.rand(*shape, dtype=torch.cfloat)))
 
+    def _plain_args(self, v, out_steps=None):
+        """What ``hip_spectral_layer`` asks of a convolution (see ``SpectralConvS._plain_args``): four complex weight blocks, no
+        bias, delta 1, no time padding, ``irfftn``'s default normalisation."""
+        T = v.shape[-1]
+        w = [self.weights1, self.weights2, self.weights3, self.weights4]
+        return w, None, 1.0, (self.modes1, self.modes2, self.modes3), 0, T, T, "backward"
+
     def forward(self, x):
         w = [self.weights1, self.weights2, self.weights3, self.weights4]
         return hip_spectral_conv(x, w, None, 1.0, (self.modes1, self.modes2, self.modes3))
+
+
+# ----------------------------------------------------------------------------- FNO3d baseline
+def hip_channel_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """``weight . x + bias`` over the channel axis of a (b, ci, *mesh) fp32 device tensor with a plain (co, ci) matrix -- a 1x1x1
+    convolution whose weight need not be a module's parameter (``MLP`` hands the product of its two matrices here).  The same
+    single-layer kernels as ``hip_pointwise(x, None, None, conv)`` (``tcfd_fno_pointwise``: co = ci, co = 1, or the rectangular
+    ci -> W kernel); differentiable w.r.t. ``x``, ``weight`` and ``bias`` through ``_PointwiseFn``.  None when the channel counts
+    are not instantiated."""
+    if not x.is_cuda or x.dtype != torch.float32 or weight.dtype != torch.float32 or weight.device != x.device:
+        return None
+    co, ci = weight.shape
+    if x.shape[1] != ci or x.shape[0] == 0:
+        return None
+    tensors = [x, weight] + ([bias] if bias is not None else [])
+    grad = torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
+    xs = x.detach().contiguous()
+    b, P, T = xs.shape[0], xs[0, 0].numel(), xs.shape[-1]
+    out = torch.empty(b, co, *xs.shape[2:], dtype=torch.float32, device=x.device)
+    w2t = weight.detach().t().contiguous()
+    b2 = bias.detach().contiguous() if bias is not None else None
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        rc = lib.tcfd_fno_pointwise_pre(xs.data_ptr(), None, out.data_ptr(), None, None, None, w2t.data_ptr(),
+                                        b2.data_ptr() if b2 is not None else None, None, None, b, ci, ci, co, P, T, 0, 0, 0, 0, 0, 0,
+                                        None, ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
+    if rc == -1 and b"not instantiated" in lib.tcfd_last_error():
+        _note_torch_modules(f"pointwise block {ci} -> {ci} -> {co}")
+        return None
+    _lib.check(rc, "tcfd_fno_pointwise")
+    if not grad:
+        return out
+    w5 = weight.reshape(co, ci, *([1] * (x.dim() - 2)))
+    return _PointwiseFn.apply(out, None, (False, None, None, 0, None), x, None, None, None, w5, bias, None, None, None, None)
+
+
+class MLP(nn.Module):
+    """Two 1x1x1 convolutions ``mlp2(act(mlp1(x)))``, ``act`` = GELU or (``activation=False``) the identity (fno/fno3d.py:119-129).
+
+    On a HIP device, fp32:
+
+    * GELU between: the fused pointwise kernels, the hidden tensor (b, mid, X, Y, T) is never formed, forward or backward.
+      Covered: the layer tail of FNO3d (in -> mid -> out all one even width 4 ... 32) and its head (even width 4 ... 32 except
+      18 / 22 / 26 / 28 / 30 -> mid in {32, 64, 128} -> 1; the forward alone takes any ``mid``).
+    * identity between: the two affine maps fold into ONE, ``w = W2 W1``, ``b = W2 b1 + b2`` (a few device tensor ops on
+      mid x in numbers), which runs as a single-layer kernel for ANY ``mid``; autograd carries the gradient of the folded
+      matrix back to the four parameters.  One dot product of length ``in`` replaces two of lengths ``in`` and ``mid``: equal
+      to rounding, not bit for bit.
+
+    Anything else runs the torch modules on the device, said once (``_note_torch_modules``)."""
+
+    def __init__(self, in_channels, out_channels, mid_channels, activation=True):
+        super().__init__()
+        self.mlp1 = nn.Conv3d(in_channels, mid_channels, 1)
+        self.mlp2 = nn.Conv3d(mid_channels, out_channels, 1)
+        self.activation = nn.GELU() if activation else nn.Identity()
+
+    def _folded(self):
+        co, cm, ci = self.mlp2.out_channels, self.mlp1.out_channels, self.mlp1.in_channels
+        w1, w2 = self.mlp1.weight.reshape(cm, ci), self.mlp2.weight.reshape(co, cm)
+        # (broadcast product + sum, not matmul: co x mid x in numbers are not worth a vendor GEMM launch)
+        w = (w2[:, :, None] * w1[None]).sum(1)
+        bias = None
+        if self.mlp1.bias is not None:
+            bias = (w2 * self.mlp1.bias[None]).sum(1)
+        if self.mlp2.bias is not None:
+            bias = self.mlp2.bias if bias is None else bias + self.mlp2.bias
+        return w, bias
+
+    def forward(self, x):
+        out = None
+        if x.is_cuda and x.dtype == torch.float32:
+            if isinstance(self.activation, nn.Identity) and type(self.mlp1) is nn.Conv3d and type(self.mlp2) is nn.Conv3d:
+                out = hip_channel_linear(x, *self._folded())
+            else:
+                out = hip_pointwise(x, self.mlp1, self.activation, self.mlp2)
+        return out if out is not None else self.mlp2(self.activation(self.mlp1(x)))
+
+
+class FNO3d(nn.Module):
+    """The FNO3d baseline (fno/fno3d.py:132-236): (b, input_channel + dim, X, Y, T) -> ``(y, None)`` with y (b, X, Y, T).
+
+    ``p`` lifts the input (the solution's first steps + the three coordinate channels) to ``width`` channels; every one of the
+    ``num_spectral_layers`` layers is ``v <- act(mlp2(GELU(mlp1(K v))) + w(v))`` with K a ``SpectralConv3d``, the hidden width of
+    the MLP equal to ``width``, and ``act`` = GELU except after the last layer (identity unless ``last_activation``); ``q`` is an
+    ``MLP(width, 1, channel_expansion)`` whose inner activation exists only with ``last_activation``.  ``padding`` pads x and y
+    circularly in front of the layers and crops behind them.  Same constructor arguments, attributes, module order (hence the
+    same initial parameters under a seed) and ``state_dict`` keys as the reference.
+
+    fp32 / complex64 on a HIP device; a CPU tensor, a float64 model or input and a wrong channel count raise.  Without
+    gradients: ``p`` on the rectangular single-layer kernel, each layer = the pruned-transform convolution + ONE fused pointwise
+    kernel, ``q`` folded (default) or on the head kernel.  Under autograd every Fourier layer is one node
+    (``hip_spectral_layer``), ``p`` and ``q`` get theirs on the backward kernels.  ``TCFD_FNO3D_FUSED=0`` runs what could be
+    assembled before this class existed -- ``SpectralConv3d`` with torch modules around it (benchmark baseline)."""
+
+    def __init__(self, modes1, modes2, modes3, width, dim=3, input_channel=10, num_spectral_layers=4, last_activation=False,
+                 padding=0, extra_mlp=True, channel_expansion=128, debug=False):
+        super().__init__()
+        self.modes1, self.modes2, self.modes3 = modes1, modes2, modes3
+        self.width = width
+        self.input_channel = input_channel
+        self.padding = padding
+        self.extra_mlp = extra_mlp
+        self.channel_expansion = channel_expansion
+        self.p = nn.Conv3d(input_channel + dim, width, 1)
+        layers = range(num_spectral_layers)
+        self.spectral_conv = nn.ModuleList([SpectralConv3d(width, width, modes1, modes2, modes3) for _ in layers])
+        self.mlp = nn.ModuleList([MLP(width, width, width) for _ in layers])
+        self.w = nn.ModuleList([nn.Conv3d(width, width, 1) for _ in layers])
+        self.activation = nn.ModuleList([nn.GELU() for _ in range(num_spectral_layers - 1)])
+        self.activation.append(nn.GELU() if last_activation else nn.Identity())
+        self.q = MLP(width, 1, channel_expansion, activation=last_activation)
+        self.debug = debug
+
+    def _check(self, x):
+        if x.dim() != 5 or x.shape[1] != self.p.in_channels:
+            raise ValueError(f"expected (b, {self.p.in_channels}, X, Y, T) = input_channel + dim channels first, got {tuple(x.shape)}")
+        bad = [n for n, prm in self.named_parameters() if prm.dtype not in (torch.float32, torch.complex64)]
+        if x.dtype != torch.float32 or bad:
+            raise TypeError("FNO3d is float32 / complex64 only (the reference's own .double() model raises too), got a "
+                            f"{x.dtype} input" + (f" and {bad[0]} in another precision" if bad else ""))
+        if not x.is_cuda:
+            raise _lib.TcfdError("expected a HIP device tensor (torch-cfd_amd has no CPU fallback)")
+
+    def forward(self, x):
+        self._check(x)
+        fused = os.environ.get("TCFD_FNO3D_FUSED", "1") != "0"
+        pad = self.padding
+        v = hip_pointwise(x, None, None, self.p) if fused else None
+        v = v if v is not None else self.p(x)
+        if pad:
+            v = F.pad(v, [0, 0, pad, pad, pad, pad], mode="circular")
+        for conv, mlp, w, act in zip(self.spectral_conv, self.mlp, self.w, self.activation):
+            if not fused:
+                v = act(mlp.mlp2(mlp.activation(mlp.mlp1(conv(v)))) + w(v))
+                continue
+            out = hip_spectral_layer(conv, v, mlp.mlp1, mlp.activation, mlp.mlp2, skip_conv=w, act2=act)
+            if out is None:       # no gradients recorded, or a grid off the library's transforms: convolution, then the fused tail
+                x1 = conv(v)
+                out = hip_pointwise(x1, mlp.mlp1, mlp.activation, mlp.mlp2, skip=v, skip_conv=w, act2=act)
+                if out is None:
+                    out = act(mlp.mlp2(mlp.activation(mlp.mlp1(x1))) + w(v))
+            v = out
+        if pad:
+            v = v[..., pad:-pad, pad:-pad, :].contiguous()
+        q = self.q
+        v = q(v) if fused else q.mlp2(q.activation(q.mlp1(v)))
+        return v.squeeze(1), None
 
 
 # ----------------------------------------------------------------------------- SFNO
