@@ -56,7 +56,7 @@ typedef struct tcfd_ns2d_plan tcfd_ns2d_plan;
 typedef struct tcfd_fno_plan tcfd_fno_plan;
 typedef struct tcfd_fvm_plan tcfd_fvm_plan;
 
-#define TCFD_ABI_VERSION 10  /* what tcfd_version() of a library built from THIS header returns */
+#define TCFD_ABI_VERSION 11  /* what tcfd_version() of a library built from THIS header returns */
 
 #ifndef TCFD_H_TYPES_ONLY   /* (the library's second compilation unit wants the types without the prototypes) */
 
@@ -66,7 +66,7 @@ const char* tcfd_last_error(void);
  * a dtype: revision 1 -> 4; round 5: 6, tcfd_fno_pointwise_pre / _bwd_saved / _profile_*, tcfd_fno_spectral_conv_pointwise
  * removed; 7: tcfd_sobolev_loss_backward, tcfd_fno_forward_trunc_kt / _inverse_trunc_kt added -- a host written against 7 needs them;
  * 8: tcfd_fvm_*; 9: tcfd_fvm_explicit_terms_vjp, tcfd_fvm_step_vjp_workspace_bytes, tcfd_fvm_step_vjp; 10: tcfd_ns2d_refine,
- * tcfd_ns2d_refine_vjp, tcfd_ns2d_refine_workspace_bytes).  A host compares it with the TCFD_ABI_VERSION it was written against BEFORE the
+ * tcfd_ns2d_refine_vjp, tcfd_ns2d_refine_workspace_bytes; 11: tcfd_grf_spectrum, tcfd_grf_spectrum_workspace_bytes).  A host compares it with the TCFD_ABI_VERSION it was written against BEFORE the
  * first call: a stale prebuilt library would otherwise be called with the wrong argument layout and return garbage
  * (torch-cfd_amd/_lib.py::load does). */
 int tcfd_version(void);
@@ -548,6 +548,23 @@ size_t tcfd_fvm_step_vjp_workspace_bytes(const tcfd_fvm_plan* plan, long batch);
 int tcfd_fvm_step_vjp(const tcfd_fvm_plan* plan, const void* saved, const void* gx, const void* gy, void* out_x, void* out_y,
                       long batch, int steps, int nstages, const double* a, const double* b, double dt, void* workspace,
                       size_t workspace_bytes, void* stream);
+
+/* ---- Gaussian random field: half spectrum of the (sub-sampled) sample, no transform -------------------------------
+ * Replaces GRF2d.sample of fno/data_gen/grf.py:79-115 followed by the driver's nearest sub-sampling and rfft2
+ * (fno/data_gen/data_gen_fno.py:195-205).  The reference takes s = Re(ifft2(sqrt_eig * c)) on an n0 x n0 mesh, keeps every
+ * (n0 / n)-th point and transforms; with V = sqrt_eig * c and H(k) = (V(k) + conj V(-k mod n0)) / 2 that is
+ *   out[kx][ky] = (n / n0)^2 * sum_{a, b < n0 / n} H(kx + a n, ky + b n),   kx < n, ky <= n / 2.
+ *   noise      (batch, 2, n0, n0) real: plane 0 = Re c, plane 1 = Im c (float for TCFD_C64, double for TCFD_C128)
+ *   sqrt_eig   (n0, n0) real of the same type: the module's table, read at k and at -k
+ *   out        (batch, n, n / 2 + 1) complex half spectrum in the layout tcfd_rfft2 writes
+ *   n          even, n0 a multiple of n; batch <= 65535
+ *   normalize  != 0: out is divided by ||s / n0||_F of the n0 mesh (grf.py:113-114; Parseval on H, partial sums combined in
+ *              a fixed order: the result is the same bit for bit from run to run).  Needs the workspace below; 0 bytes
+ *              without normalize.
+ * The imaginary parts of the self-conjugate modes are exactly 0 for n0 = n. */
+size_t tcfd_grf_spectrum_workspace_bytes(long batch, int n, int normalize);
+int tcfd_grf_spectrum(const void* noise, const void* sqrt_eig, void* out, long batch, int n0, int n, int dtype, int normalize,
+                      void* workspace, size_t workspace_bytes, void* stream);
 
 #endif /* TCFD_H_TYPES_ONLY */
 

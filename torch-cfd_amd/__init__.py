@@ -19,6 +19,7 @@ from .equations import (  # noqa: F401
 )
 from .forcings import FieldArray, ForcingFn, KolmogorovForcing, SimpleSolenoidalForcing, SinCosForcing  # noqa: F401
 from .solvers import get_trajectory_imex  # noqa: F401
+from .grf import GRF2d  # noqa: F401
 from .fvm import NavierStokes2DFVMProjection, PressureProjection, RKStepper, get_trajectory_fvm  # noqa: F401
 from .spectral import (  # noqa: F401
     brick_wall_filter_2d,

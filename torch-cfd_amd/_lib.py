@@ -24,10 +24,11 @@ CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_NAME = "libtcfd_hip.so"
 LIB_PATH = os.path.join(CSRC, LIB_NAME)
-SOURCES = ("tcfd_ns2d.hip", "tcfd_fno.hip", "tcfd_fno_pw.hip", "tcfd_fno_tiles.hip", "tcfd_fno3d.hip", "tcfd_loss.hip", "tcfd_fvm.hip")
+SOURCES = ("tcfd_ns2d.hip", "tcfd_fno.hip", "tcfd_fno_pw.hip", "tcfd_fno_tiles.hip", "tcfd_fno3d.hip", "tcfd_loss.hip", "tcfd_fvm.hip",
+           "tcfd_grf.hip")
 
 TCFD_C64, TCFD_C128 = 0, 1
-ABI_VERSION = 10  # TCFD_ABI_VERSION of include/tcfd.h the SIGNATURES table below was written against
+ABI_VERSION = 11  # TCFD_ABI_VERSION of include/tcfd.h the SIGNATURES table below was written against
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -82,7 +83,8 @@ JOBS = (("tcfd_ns2d.hip", ("-DTCFD_UNIT=0",), "tcfd_ns2d.o"),
         ("tcfd_fno3d.hip", (), "tcfd_fno3d.o"),
         ("tcfd_loss.hip", (), "tcfd_loss.o"),
         ("tcfd_fvm.hip", ("-DTCFD_UNIT=0",), "tcfd_fvm.o"),
-        ("tcfd_fvm.hip", ("-DTCFD_UNIT=1",), "tcfd_fvm_f32.o"))
+        ("tcfd_fvm.hip", ("-DTCFD_UNIT=1",), "tcfd_fvm_f32.o"),
+        ("tcfd_grf.hip", (), "tcfd_grf.o"))
 
 
 def _build_locked(srcs, verbose):
@@ -204,6 +206,8 @@ SIGNATURES = {
     "tcfd_fvm_explicit_terms_vjp": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _d, _vp]),
     "tcfd_fvm_step_vjp_workspace_bytes": (_sz, [_vp, _l]),
     "tcfd_fvm_step_vjp": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _dp, _dp, _d, _vp, _sz, _vp]),
+    "tcfd_grf_spectrum_workspace_bytes": (_sz, [_l, _i, _i]),
+    "tcfd_grf_spectrum": (_i, [_vp, _vp, _vp, _l, _i, _i, _i, _i, _vp, _sz, _vp]),
 }
 
 

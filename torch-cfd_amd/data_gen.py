@@ -116,13 +116,74 @@ def generate_kolmogorov_dataset(n: int, total_samples: int, batch_size: int, dt:
                              initial_vorticity, diam, random_state, subsample, dtype, cdtype, device, dst, path, stats, as_rank0_of)
 
 
+def fno_sample_seeds(random_state: int, start: int, count: int) -> list:
+    """Seeds of the samples with global indices start .. start + count - 1 of the FNO data set: ``random_state`` + the global
+    index (fno/data_gen/data_gen_fno.py:196), whatever the batch size and however the samples are cut across ranks."""
+    return [random_state + g for g in range(start, start + count)]
+
+
+def generate_fno_dataset(n: int, total_samples: int, batch_size: int, dt: float, warmup_steps: int, total_steps: int,
+                         record_every_steps: int, viscosity: float = 1e-3, diam: float = 1.0, scale: float = 0.1,
+                         peak_wavenumber: float = 4, alpha: float = 2.5, tau: float = 7.0, normalize: bool = False,
+                         replicable_init: bool = False, extra_vars: bool = True, random_state: int = 0, subsample: int = 1,
+                         dtype: torch.dtype = torch.float32, cdtype: torch.dtype = torch.complex64, device="cuda", dst: int = 0,
+                         path: Optional[str] = None, stats: Optional[dict] = None,
+                         as_rank0_of: Optional[int] = None) -> Optional[Dict[str, torch.Tensor]]:
+    """The FNO-paper data set (``fnodata_extra_64x64_N1280_v1e-3_T50_steps100_alpha2.5_tau7.pt``): the loop of
+    fno/data_gen/data_gen_fno.py:152-252 -- vorticity forcing ``scale * (sin(k (x + y)) + cos(k (x + y)))`` (``:154-160``),
+    ``NavierStokes2DSpectral(smooth=True)`` stepped by ``IMEXStepper(order=2)`` (``:171-177``), a Gaussian random field
+    ``GRF2d(alpha, tau, normalize)`` per sample as initial vorticity, seeded ``random_state`` + global sample index
+    (``:163-170``, ``:196-205``), ``warmup_steps`` unrecorded steps (``:209-220``), ``get_trajectory_imex`` with a record every
+    ``record_every_steps`` (``:223-230``), irfft2 -> cast -> bilinear subsample (``:232-243``), ``random_states`` (``:248``).
+    Same dataset dict, ``path`` / ``stats``, hand-over and multi-rank split as ``generate_mcwilliams_dataset``.
+
+    ``replicable_init`` draws every field at 2048^2 and keeps every (2048 / n)-th point (the driver's ``--replicable-init``), so
+    a seed gives the same flow at every n.  Either way the initial half spectrum comes straight from the noise
+    (``GRF2d.sample_hat``: no transform).  ``extra_vars=False`` stores empty ``vort_t`` / ``stream`` / ``residual`` tensors, as
+    the driver does without ``--extra-vars`` (``:245-247``).
+
+    The reference driver does not run as written: it builds ``step_fn = IMEXStepper(order=2)`` (``:171``) and never passes it
+    to the operator, so ``ns2d.step`` calls ``None``.  The evident intent ``solver=step_fn`` is what runs here."""
+    from .equations import IMEXStepper
+    from .forcings import SinCosForcing
+    from .grf import GRF2d
+
+    n0 = 2048 if replicable_init else n
+    if n > 2048:
+        raise ValueError(f"Grid size {n} is larger than the maximum allowed 2048")
+    grf = GRF2d(n=n, alpha=alpha, tau=tau, normalize=normalize, device=device, dtype=torch.float64)
+
+    def make_operator(grid):
+        forcing = SinCosForcing(grid=grid, scale=scale, diam=diam, k=peak_wavenumber, vorticity=True)
+        return NavierStokes2DSpectral(viscosity=viscosity, grid=grid, smooth=True, forcing_fn=forcing, solver=IMEXStepper(order=2))
+
+    def initial_spectrum(grid, start, count, device):
+        real = torch.get_default_dtype()
+        return grf.sample_hat(fno_sample_seeds(random_state, start, count), n, n0, device=device).to(
+            torch.complex128 if real == torch.float64 else torch.complex64)
+
+    full = _generate_dataset(n, total_samples, batch_size, dt, warmup_steps, total_steps, record_every_steps, make_operator,
+                             initial_spectrum, diam, random_state, subsample, dtype, cdtype, device, dst, None, stats, as_rank0_of,
+                             spectral_initial_condition=True)
+    if full is None:
+        return None
+    if not extra_vars:
+        for key in ("vort_t", "stream", "residual"):
+            full[key] = torch.empty(0)
+    if path is not None:
+        torch.save(full, path)
+    return full
+
+
 def _generate_dataset(n: int, total_samples: int, batch_size: int, dt: float, warmup_steps: int, total_steps: int,
                       record_every_steps: int, make_operator, initial_vorticity, diam: float, random_state: int,
                       subsample: int, dtype: torch.dtype, cdtype: torch.dtype, device, dst: int, path: Optional[str],
-                      stats: Optional[dict], as_rank0_of: Optional[int]) -> Optional[Dict[str, torch.Tensor]]:
-    """The batch loop both drivers share (fno/data_gen/data_gen_McWilliams2d.py:119-171, data_gen_Kolmogorov2d.py:134-192):
-    ``make_operator(grid)`` builds the equation, ``initial_vorticity(grid, start, count, device)`` the (count, n, n) physical
-    initial vorticity of the samples with global indices start .. start + count - 1."""
+                      stats: Optional[dict], as_rank0_of: Optional[int],
+                      spectral_initial_condition: bool = False) -> Optional[Dict[str, torch.Tensor]]:
+    """The batch loop the drivers share (fno/data_gen/data_gen_McWilliams2d.py:119-171, data_gen_Kolmogorov2d.py:134-192,
+    data_gen_fno.py:188-252): ``make_operator(grid)`` builds the equation, ``initial_vorticity(grid, start, count, device)``
+    the (count, n, n) physical initial vorticity of the samples with global indices start .. start + count - 1 -- or, with
+    ``spectral_initial_condition``, its (count, n, n/2 + 1) half spectrum, which then goes to the stepper as it is."""
     import time
 
     import torch.distributed as dist
@@ -159,7 +220,9 @@ def _generate_dataset(n: int, total_samples: int, batch_size: int, dt: float, wa
     t_setup = time.perf_counter()
     try:
         for start, count in layout[rank]:
-            w = plan.rfft2(initial_vorticity(grid, start, count, device))
+            w = initial_vorticity(grid, start, count, device)
+            if not spectral_initial_condition:
+                w = plan.rfft2(w)
             handover.start_allocation()     # page-lock the result now: under the warm-up steps, not under the CPU noise above
             if warmup_steps > 0:
                 w, _ = op._fused_steps(w, dt, warmup_steps, want_dwdt=False)
