@@ -56,7 +56,7 @@ typedef struct tcfd_ns2d_plan tcfd_ns2d_plan;
 typedef struct tcfd_fno_plan tcfd_fno_plan;
 typedef struct tcfd_fvm_plan tcfd_fvm_plan;
 
-#define TCFD_ABI_VERSION 11  /* what tcfd_version() of a library built from THIS header returns */
+#define TCFD_ABI_VERSION 12  /* what tcfd_version() of a library built from THIS header returns */
 
 #ifndef TCFD_H_TYPES_ONLY   /* (the library's second compilation unit wants the types without the prototypes) */
 
@@ -66,7 +66,9 @@ const char* tcfd_last_error(void);
  * a dtype: revision 1 -> 4; round 5: 6, tcfd_fno_pointwise_pre / _bwd_saved / _profile_*, tcfd_fno_spectral_conv_pointwise
  * removed; 7: tcfd_sobolev_loss_backward, tcfd_fno_forward_trunc_kt / _inverse_trunc_kt added -- a host written against 7 needs them;
  * 8: tcfd_fvm_*; 9: tcfd_fvm_explicit_terms_vjp, tcfd_fvm_step_vjp_workspace_bytes, tcfd_fvm_step_vjp; 10: tcfd_ns2d_refine,
- * tcfd_ns2d_refine_vjp, tcfd_ns2d_refine_workspace_bytes; 11: tcfd_grf_spectrum, tcfd_grf_spectrum_workspace_bytes).  A host compares it with the TCFD_ABI_VERSION it was written against BEFORE the
+ * tcfd_ns2d_refine_vjp, tcfd_ns2d_refine_workspace_bytes; 11: tcfd_grf_spectrum, tcfd_grf_spectrum_workspace_bytes;
+ * 12: tcfd_residual_loss, tcfd_residual_loss_backward, tcfd_residual_loss_supported, tcfd_residual_workspace_bytes, tcfd_lp_sums,
+ * tcfd_lp_sums_bwd, tcfd_lp_sums_workspace_bytes, tcfd_h1_sums, tcfd_h1_sums_bwd, tcfd_h1_sums_workspace_bytes).  A host compares it with the TCFD_ABI_VERSION it was written against BEFORE the
  * first call: a stale prebuilt library would otherwise be called with the wrong argument layout and return garbage
  * (torch-cfd_amd/_lib.py::load does). */
 int tcfd_version(void);
@@ -483,6 +485,47 @@ int tcfd_sobolev_loss(const tcfd_loss_plan* p, const void* x, const void* y, con
 int tcfd_sobolev_loss_backward(const tcfd_loss_plan* p, const void* x, const void* y, const void* wf, const void* sums,
                                const void* gout, long batch, int nt, int nfields, int relative, int mesh_weighted,
                                int time_average, int reduction, void* grad, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- the other losses of fno/losses.py (csrc/tcfd_residual.hip) -----------------------------------------------------
+ * ResidualLoss (fno/losses.py:367-467): the residual of the vorticity equation over a predicted block, on a tcfd_loss_plan
+ * (its grids and precisions).  w, f: (batch, n, n, nt) real, time last, f may be NULL.  Tables of the data's precision, built by
+ * the caller from the module's own (so that their rounding is the module's): m2pi[n] = 2 pi k, lap[n * n] = the patched
+ * -4 pi^2 (kx^2 + ky^2), ckt[nt] = 2 pi kt, twt[nt] = exp(-2 pi i j / nt) (complex).  scale = fft-norm factor / (batch n n):
+ * out[0] = scale * sum over (b, kx) of the 2-norm over (ky, kt) of Re(2 pi i kt w^ + conv^ - visc lap w^ - f^) with unnormalised
+ * transforms.  rows: (batch, n) doubles, the squared row norms, kept by the caller for the backward call.  Seven launches, no
+ * atomics: the same bits from run to run.  Workspace: tcfd_residual_workspace_bytes(plan, batch, nt, backward).
+ * backward: grad_w and / or grad_f (either may be NULL) = gout[0] * d out / d w, d out / d f; everything but `rows` is
+ * recomputed.  A row of norm zero contributes nothing.  tcfd_residual_loss_supported: 0 when nt exceeds what the time
+ * transform's workgroup holds (128). */
+size_t tcfd_residual_workspace_bytes(const tcfd_loss_plan* p, long batch, int nt, int backward);
+int tcfd_residual_loss_supported(const tcfd_loss_plan* p, int nt);
+int tcfd_residual_loss(const tcfd_loss_plan* p, const void* w, const void* f, const void* m2pi, const void* lap, const void* ckt,
+                       const void* twt, double visc, double scale, long batch, int nt, void* out, void* rows, void* ws,
+                       size_t ws_bytes, void* stream);
+int tcfd_residual_loss_backward(const tcfd_loss_plan* p, const void* w, const void* f, const void* m2pi, const void* lap,
+                                const void* ckt, const void* twt, double visc, double scale, const void* rows, const void* gout,
+                                long batch, int nt, void* grad_w, void* grad_f, void* ws, size_t ws_bytes, void* stream);
+
+/* p-norm sums of LpLoss, L2Loss2d and BochnerNorm: x, y contiguous, viewed as (outer, reduce, inner); dtype TCFD_C64: float,
+ * TCFD_C128: double.  sum_diff[outer * inner] = sum over reduce of |x - y|^p (y NULL: |x|^p), sum_y (optional) = that of |y|^p;
+ * both doubles.  Any finite p > 0 (1 and 2 without pow); inner <= 256, outer <= 65535.  One pass over x and y, double
+ * accumulators, two stages in a fixed order.  bwd: grad_x = cot_diff[o][i] d|x - y|^p / dx, grad_y = -that + cot_y[o][i]
+ * d|y|^p / dy (cot_*: doubles; grad_x, grad_y, cot_y optional). */
+size_t tcfd_lp_sums_workspace_bytes(long outer, long reduce, int inner);
+int tcfd_lp_sums(const void* x, const void* y, void* sum_diff, void* sum_y, long outer, long reduce, int inner, double p, int dtype,
+                 void* ws, size_t ws_bytes, void* stream);
+int tcfd_lp_sums_bwd(const void* x, const void* y, const void* cot_diff, const void* cot_y, void* grad_x, void* grad_y, long outer,
+                     long reduce, int inner, double p, int dtype, void* stream);
+
+/* The H^1 term of L2Loss2d (fno/losses.py:113-126): preds (batch, channels, n1, n2), tgrad (batch, 2 channels, n1, n2) with the
+ * differences along dim -2 of all channels first.  ksqrt: the square root of the diffusion constant -- kmode 0: none, 1: one
+ * value, 2: (batch, 1, n1, n2).  s1[batch] = sum (ksqrt (cd(preds) - tgrad))^2 with cd the zero-padded central difference
+ * (u[i+1] - u[i-1]) / 2 / h, s2[batch] = sum ksqrt tgrad^2; doubles.  bwd: grad = cot[batch] * d s1 / d preds. */
+size_t tcfd_h1_sums_workspace_bytes(long batch, int channels, int n1, int n2);
+int tcfd_h1_sums(const void* preds, const void* tgrad, const void* ksqrt, int kmode, void* s1, void* s2, long batch, int channels,
+                 int n1, int n2, double h, int dtype, void* ws, size_t ws_bytes, void* stream);
+int tcfd_h1_sums_bwd(const void* preds, const void* tgrad, const void* ksqrt, int kmode, const void* cot, void* grad, long batch,
+                     int channels, int n1, int n2, double h, int dtype, void* stream);
 
 /* STREAM-style device probe (measurement aid, SURVEY 8d "verify with a device STREAM-style probe"): `iters`
  * launches of a 16-byte-per-lane grid-stride kernel over `bytes` (a multiple of 16) of caller-owned device memory,

@@ -25,10 +25,10 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_NAME = "libtcfd_hip.so"
 LIB_PATH = os.path.join(CSRC, LIB_NAME)
 SOURCES = ("tcfd_ns2d.hip", "tcfd_fno.hip", "tcfd_fno_pw.hip", "tcfd_fno_tiles.hip", "tcfd_fno3d.hip", "tcfd_loss.hip", "tcfd_fvm.hip",
-           "tcfd_grf.hip")
+           "tcfd_grf.hip", "tcfd_residual.hip")
 
 TCFD_C64, TCFD_C128 = 0, 1
-ABI_VERSION = 11  # TCFD_ABI_VERSION of include/tcfd.h the SIGNATURES table below was written against
+ABI_VERSION = 12  # TCFD_ABI_VERSION of include/tcfd.h the SIGNATURES table below was written against
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -84,7 +84,10 @@ JOBS = (("tcfd_ns2d.hip", ("-DTCFD_UNIT=0",), "tcfd_ns2d.o"),
         ("tcfd_loss.hip", (), "tcfd_loss.o"),
         ("tcfd_fvm.hip", ("-DTCFD_UNIT=0",), "tcfd_fvm.o"),
         ("tcfd_fvm.hip", ("-DTCFD_UNIT=1",), "tcfd_fvm_f32.o"),
-        ("tcfd_grf.hip", (), "tcfd_grf.o"))
+        ("tcfd_grf.hip", (), "tcfd_grf.o"),
+        # the residual loss, twice as well: unit 0 = C ABI + float64 kernels + the small losses, unit 1 = float32 kernels
+        ("tcfd_residual.hip", ("-DTCFD_RES_UNIT=0",), "tcfd_residual.o"),
+        ("tcfd_residual.hip", ("-DTCFD_RES_UNIT=1",), "tcfd_residual_f32.o"))
 
 
 def _build_locked(srcs, verbose):
@@ -208,6 +211,16 @@ SIGNATURES = {
     "tcfd_fvm_step_vjp": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _dp, _dp, _d, _vp, _sz, _vp]),
     "tcfd_grf_spectrum_workspace_bytes": (_sz, [_l, _i, _i]),
     "tcfd_grf_spectrum": (_i, [_vp, _vp, _vp, _l, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "tcfd_residual_workspace_bytes": (_sz, [_vp, _l, _i, _i]),
+    "tcfd_residual_loss_supported": (_i, [_vp, _i]),
+    "tcfd_residual_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _l, _i, _vp, _vp, _vp, _sz, _vp]),
+    "tcfd_residual_loss_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _vp, _vp, _l, _i, _vp, _vp, _vp, _sz, _vp]),
+    "tcfd_lp_sums_workspace_bytes": (_sz, [_l, _l, _i]),
+    "tcfd_lp_sums": (_i, [_vp, _vp, _vp, _vp, _l, _l, _i, _d, _i, _vp, _sz, _vp]),
+    "tcfd_lp_sums_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _i, _d, _i, _vp]),
+    "tcfd_h1_sums_workspace_bytes": (_sz, [_l, _i, _i, _i]),
+    "tcfd_h1_sums": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _l, _i, _i, _i, _d, _i, _vp, _sz, _vp]),
+    "tcfd_h1_sums_bwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _l, _i, _i, _i, _d, _i, _vp]),
 }
 
 

@@ -27,6 +27,7 @@
 
 #include "../../include/tcfd.h"
 #include "tcfd_fft.hpp"
+#include "tcfd_loss_plan.hpp"
 
 using namespace tcfd;
 
@@ -39,11 +40,6 @@ int tcfd_set_error(int code, const char* fmt, ...);  // defined in tcfd_ns2d.hip
         if (e_ != hipSuccess) return FAIL(TCFD_EHIP, "%s: %s", #expr, hipGetErrorString(e_));      \
     } while (0)
 
-struct tcfd_loss_plan {
-    int n;       // square grid: 2^k in [16, 1024], 3 * 2^k in [96, 768] or 5 * 2^k in [80, 640]
-    int dtype;   // TCFD_C64: float data, TCFD_C128: double data
-    void* tw;    // [n] exp(-2 pi i k / n) in the plan's precision
-};
 
 typedef unsigned int b128 __attribute__((ext_vector_type(4)));
 

@@ -2126,4 +2126,4 @@ def make_graphed_training_step(model: nn.Module, loss_fn, optimizer: torch.optim
 
 
 # ----------------------------------------------------------------------------- loss: torch-cfd_amd/losses.py (fno/losses.py)
-from .losses import SobolevLoss, hip_weighted_sqnorm  # noqa: E402,F401
+from .losses import BochnerNorm, L2Loss2d, LpLoss, ResidualLoss, SobolevLoss, central_diff, hip_weighted_sqnorm  # noqa: E402,F401
