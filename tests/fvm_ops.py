@@ -107,3 +107,100 @@ def kolmogorov_staggered(n, wave, scale=1.0, L=2 * math.pi, dtype=torch.float64)
     y = (torch.arange(n, dtype=dtype) + 0.5) * h
     fx = scale * torch.sin(wave * (2 * math.pi / L) * y)[None, :].expand(n, n).contiguous()
     return fx, torch.zeros_like(fx)
+
+
+# ---- inputs at the edges (tests/golden/make_golden_fvm.py edges() and the GPU tests at sizes no golden covers)
+EDGE_STARTS = ("rest", "blocks", "checker", "integers")
+
+# explicit tableaux beyond the named methods: two earlier stages feeding one stage state, negative weights, a zero row
+TABLEAUX = {
+    "rule38": {"a": [[1 / 3], [-1 / 3, 1.0], [1.0, -1.0, 1.0]], "b": [1 / 8, 3 / 8, 3 / 8, 1 / 8]},
+    "ssprk3": {"a": [[1.0], [1 / 4, 1 / 4]], "b": [1 / 6, 1 / 6, 2 / 3]},
+    "zero_row": {"a": [[0.0], [0.0, 1 / 2]], "b": [0.0, 0.0, 1.0]},
+}
+
+
+OPTIONAL_TERMS = ("plain", "dense", "negdrag")   # the a2_* groups of tests/golden/fvm_edges.npz
+
+
+def degenerate_start(name, n, seed=0, dtype=torch.float64):
+    """(2, n, n) velocity of small integers, so that the van Leer limiter's ties (face velocity w == 0, difference
+    d == 0) are exact in any precision: rest; 4 x 4 blocks of {-1, 0, 1, 2}; a +-1 checkerboard (w == 0 on every face,
+    d != 0); integers in [-2, 2]."""
+    gen = torch.Generator().manual_seed(seed)
+    if name == "rest":
+        u = torch.zeros(2, n, n)
+    elif name == "blocks":
+        u = torch.randint(-1, 3, (2, n // 4, n // 4), generator=gen).repeat_interleave(4, -2).repeat_interleave(4, -1)
+    elif name == "checker":
+        i = torch.arange(n)
+        sign = 1 - 2 * ((i[:, None] + i[None, :]) % 2)
+        u = torch.stack([sign, -sign])
+    elif name == "integers":
+        u = torch.randint(-2, 3, (2, n, n), generator=gen)
+    else:
+        raise ValueError(name)
+    return u.to(dtype)
+
+
+def cotangent(shape, seed, dtype=torch.float64):
+    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64).to(dtype)
+
+
+class Physics:
+    """One configuration of the solver, for the restatement and for the package alike: domain [0, length]^2, n x n."""
+
+    def __init__(self, n, length=2 * math.pi, nu=1e-3, drag=0.1, density=1.0, wave=2):
+        self.n, self.length, self.nu, self.drag, self.density, self.wave = n, length, nu, drag, density, wave   # wave None: unforced
+        self.h = length / n
+
+    @classmethod
+    def of_golden(cls, g, group, n=None):
+        """The physics of one group (``a1``, ``a2_plain``, ``a2_dense``, ``a3``) of tests/golden/fvm_edges.npz, at the
+        golden's n or another."""
+        n = int(g["n"]) if n is None else n
+        if group.startswith("a2_"):
+            return cls(n, float(g[f"{group}_length"]), float(g[f"{group}_nu"]), float(g[f"{group}_drag"]),
+                       float(g[f"{group}_density"]), int(g["wave"]) if bool(g[f"{group}_forced"]) else None)
+        return cls(n, 2 * math.pi, float(g["a1_nu"]), float(g["a1_drag"]), 1.0, int(g["wave"]))
+
+    def tables(self, device="cpu", dtype=torch.float64):
+        """(force / density, inverse eigenvalues): formed in fp64 and then rounded to `dtype`, as the package's plan does."""
+        force = None
+        if self.wave is not None:
+            force = tuple((f / self.density).to(device, dtype) for f in kolmogorov_staggered(self.n, self.wave, L=self.length))
+        inv = inverse_eigenvalues(self.n, self.h)
+        return force, inv.to(device, torch.complex128 if dtype == torch.float64 else torch.complex64)
+
+    def explicit(self, dt, device="cpu", dtype=torch.float64):
+        force, _ = self.tables(device, dtype)
+        return lambda u: explicit_terms(u[0], u[1], dt, self.h, self.nu / self.density, self.drag, force)
+
+    def projection(self, device="cpu", dtype=torch.float64):
+        _, inv = self.tables(device, dtype)
+        return lambda u: project(u[0], u[1], self.h, inv)
+
+    def rollout(self, a, b, dt, steps, device="cpu", dtype=torch.float64):
+        force, inv = self.tables(device, dtype)
+
+        def run(u):
+            ux, uy = u
+            for _ in range(steps):
+                ux, uy = step(ux, uy, dt, a, b, self.h, self.nu / self.density, self.drag, force, inv)
+            return ux, uy
+        return run
+
+    def grid(self):
+        import torch_cfd_amd as tc
+
+        return tc.Grid(shape=(self.n, self.n), domain=((0, self.length), (0, self.length)))
+
+    def equation(self, solver=None):
+        """The package's equation of this configuration."""
+        import torch_cfd_amd as tc
+
+        grid = self.grid()
+        forcing = None
+        if self.wave is not None:
+            forcing = tc.KolmogorovForcing(grid=grid, diam=self.length, wave_number=self.wave, offsets=grid.cell_faces)
+        return tc.NavierStokes2DFVMProjection(self.nu, grid, drag=self.drag, density=self.density, forcing=forcing, solver=solver)

@@ -16,6 +16,7 @@ import torch
 REF = "/root/reference"
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REF)
+sys.path.insert(0, os.path.dirname(HERE))   # tests/: fvm_ops holds the degenerate starts and the tableaux the tests share
 
 from torch_cfd import boundaries, grids  # noqa: E402
 from torch_cfd.equations import stable_time_step  # noqa: E402
@@ -23,6 +24,8 @@ from torch_cfd.forcings import KolmogorovForcing  # noqa: E402
 from torch_cfd.fvm import NavierStokes2DFVMProjection, RKStepper, convect, diffuse_velocity  # noqa: E402
 from torch_cfd.initial_conditions import filtered_velocity_field  # noqa: E402
 from torch_cfd.pressure import PressureProjection  # noqa: E402
+
+import fvm_ops as F  # noqa: E402
 
 L = 2 * np.pi
 METHODS = ("forward_euler", "midpoint", "heun_rk2", "classic_rk4")
@@ -145,12 +148,109 @@ def notebook():
             save(f"v{target}", data=a.astype(np.float32))
 
 
+def state_of(arrays, like, leaves=False):
+    """GridVariableVector of the given arrays with the offsets and bcs of `like` (fresh leaves that require grad on request)."""
+    vs = [grids.GridVariable(grids.GridArray(a.clone().requires_grad_(leaves), c.offset, c.grid), c.bc)
+          for a, c in zip(arrays, like)]
+    return grids.GridVariableVector(vs), [v.data for v in vs]
+
+
+def vjp(fn, arrays, like, cot):
+    """Gradient of sum(cot * fn(state)) with respect to the two velocity arrays."""
+    v, leaves = state_of(arrays, like, leaves=True)
+    out = fn(v)
+    loss = sum((c.data * g).sum() for c, g in zip(out, cot))
+    return np.stack([g.numpy() for g in torch.autograd.grad(loss, leaves)])
+
+
+def edges():
+    """n = 16, fp64: the van Leer limiter's ties (A1), the optional terms (A2) and general tableaux (A3).  Every entry
+    stores its inputs, cotangent and dt beside the reference's results."""
+    n, wave = 16, 2
+    bc = boundaries.HomogeneousBoundaryConditions(((boundaries.BCType.PERIODIC,) * 2,) * 2)
+
+    def build(length, nu, drag, density, forced, stepper):
+        grid = grids.Grid((n, n), domain=((0, length), (0, length)))
+        forcing = KolmogorovForcing(diam=length, wave_number=wave, grid=grid, offsets=((1.0, 0.5), (0.5, 1.0))) if forced else None
+        eq = NavierStokes2DFVMProjection(viscosity=nu, grid=grid, bcs=(bc, bc), density=density, drag=drag, forcing=forcing,
+                                         solver=stepper)
+        return grid, eq
+
+    def named(method):
+        return RKStepper.from_method(method=method, requires_grad=False, dtype=torch.float32)
+
+    def rollout(stepper, eq, dt, k):
+        def fn(v):
+            for _ in range(k):
+                v = stepper.forward(v, dt, equation=eq)
+            return v
+        return fn
+
+    out = {"n": n, "wave": wave, "starts": np.array(F.EDGE_STARTS)}
+    # ---- A1: degenerate starts, nu = 1e-3, drag 0.1, Kolmogorov k = 2, dt = h / 4
+    rk4, euler = named("classic_rk4"), named("forward_euler")
+    grid, eq = build(L, 1e-3, 0.1, 1.0, True, rk4)
+    like = filtered_velocity_field(grid, 2.0, 3.0, iterations=3, random_state=0)
+    dt = 0.25 * min(grid.step)
+    out["a1_dt"], out["a1_nu"], out["a1_drag"] = dt, 1e-3, 0.1
+    for si, name in enumerate(F.EDGE_STARTS):
+        u = F.degenerate_start(name, n, seed=100 + si)
+        cot = F.cotangent((2, n, n), 200 + si)
+        v, _ = state_of(u, like)
+        out[f"a1_{name}_u0"] = u.numpy()
+        out[f"a1_{name}_cot"] = cot.numpy()
+        with torch.no_grad():
+            out[f"a1_{name}_explicit"] = arr(eq.explicit_terms(v, dt))
+            out[f"a1_{name}_classic_rk4_1"] = arr(run(v, rk4, eq, dt, 1))
+            out[f"a1_{name}_classic_rk4_3"] = arr(run(v, rk4, eq, dt, 3))
+        out[f"a1_{name}_explicit_vjp"] = vjp(lambda w: eq.explicit_terms(w, dt), u, like, cot)
+        out[f"a1_{name}_forward_euler_vjp"] = vjp(rollout(euler, eq, dt, 1), u, like, cot)
+    # ---- A2: optional terms, smooth start (seed 0), nu = 1e-2, no drag
+    # ("negdrag": a negative drag is no drag, `if self.drag > 0`; only there does a drag term applied regardless show)
+    for ti, (tag, length, density, forced, drag) in enumerate((("plain", L, 1.0, False, 0.0), ("dense", 1.0, 2.0, True, 0.0),
+                                                                ("negdrag", L, 1.0, False, -0.1))):
+        grid, eq = build(length, 1e-2, drag, density, forced, rk4)
+        like = filtered_velocity_field(grid, 2.0, 3.0, iterations=3, random_state=0)
+        u = torch.stack([c.data.detach() for c in like])
+        dt = 0.25 * min(grid.step)
+        cot = F.cotangent((2, n, n), 300 + ti)
+        out[f"a2_{tag}_length"], out[f"a2_{tag}_density"], out[f"a2_{tag}_forced"] = length, density, forced
+        out[f"a2_{tag}_nu"], out[f"a2_{tag}_drag"] = 1e-2, drag
+        out[f"a2_{tag}_dt"], out[f"a2_{tag}_u0"], out[f"a2_{tag}_cot"] = dt, u.numpy(), cot.numpy()
+        with torch.no_grad():
+            out[f"a2_{tag}_explicit"] = arr(eq.explicit_terms(like, dt))
+            out[f"a2_{tag}_classic_rk4_3"] = arr(run(like, rk4, eq, dt, 3))
+        out[f"a2_{tag}_classic_rk4_3_vjp"] = vjp(rollout(rk4, eq, dt, 3), u, like, cot)
+    # ---- A3: general tableaux (fp64 parameters), smooth start, the physics of A1
+    grid, eq = build(L, 1e-3, 0.1, 1.0, True, None)
+    like = filtered_velocity_field(grid, 2.0, 3.0, iterations=3, random_state=0)
+    u = torch.stack([c.data.detach() for c in like])
+    dt = 0.25 * min(grid.step)
+    cot = F.cotangent((2, n, n), 400)
+    out["a3_dt"], out["a3_u0"], out["a3_cot"] = dt, u.numpy(), cot.numpy()
+    for name, tableau in F.TABLEAUX.items():
+        stepper = RKStepper(tableau=tableau, dtype=torch.float64)
+        s = len(tableau["b"])
+        a = np.zeros((s, s))
+        for i, row in enumerate(tableau["a"]):
+            a[i + 1, :len(row)] = row
+        out[f"a3_{name}_a"], out[f"a3_{name}_b"] = a, np.array(tableau["b"])
+        out[f"a3_{name}_1"] = arr(run(like, stepper, eq, dt, 1))
+        out[f"a3_{name}_3"] = arr(run(like, stepper, eq, dt, 3))
+        out[f"a3_{name}_3_vjp"] = vjp(rollout(stepper, eq, dt, 3), u, like, cot)
+    for k, v in out.items():
+        a = np.asarray(v)
+        assert a.dtype.kind in "US" or np.isfinite(a).all(), k
+    np.savez_compressed(os.path.join(HERE, "fvm_edges.npz"), **out)
+
+
 if __name__ == "__main__":
     torch.set_default_dtype(torch.float64)
     torch.set_num_threads(min(16, os.cpu_count() or 1))
     tables()
     small()
     notebook()
+    edges()
     for f in sorted(os.listdir(HERE)):
         if f.startswith("fvm_") and f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(HERE, f)))

@@ -203,3 +203,225 @@ def test_default_offset_forcing_tables_are_unchanged(fp64_default):
         wave = torch.sin(4.0 * y) if not swap else torch.sin(4.0 * x)
         want = (wave, torch.zeros_like(wave)) if not swap else (torch.zeros_like(wave), wave)
         assert torch.equal(fx.data, want[0]) and torch.equal(fy.data, want[1])
+
+
+# ----------------------------------------------------------------------------- the edges: limiter ties, every size family,
+# optional terms, general tableaux, fp32 at the large transforms, batch independence, unsupported sizes
+SIZES = (8, 16, 32, 80, 96, 128, 160, 192)   # every size family; 80, 96, 160, 192 leave the last 64-wide x-block partly masked
+
+
+def _rk4(dtype=torch.float32):
+    import torch_cfd_amd as tc
+
+    return tc.RKStepper.from_method(method="classic_rk4", dtype=dtype)
+
+
+def _smooth(ph, seeds, dtype=torch.float64):
+    from torch_cfd_amd import initial_conditions as ic
+
+    ux, uy = ic.filtered_velocity_field(ph.grid(), 2.0, 3.0, random_state=0, device=DEV, batch_seeds=list(seeds))
+    return ux.to(dtype), uy.to(dtype)
+
+
+def _dev(a, dtype=torch.float64):
+    a = torch.as_tensor(a).to(DEV, dtype)
+    return a[..., 0, :, :].contiguous(), a[..., 1, :, :].contiguous()
+
+
+def _finite(u):
+    return all(torch.isfinite(c).all().item() for c in u)
+
+
+def _band_ok(got, want, n, bound):
+    """The bar on the whole field and, where the last x-block is partly masked, on its columns alone."""
+    got, want = torch.stack(got), torch.stack(want)
+    got, want = got.cpu(), want.cpu()
+    errs = [rel_l2(got, want)]
+    if n > 64 and n % 64:
+        errs.append(rel_l2(got[..., :, 64:], want[..., :, 64:]))
+    return max(errs) <= bound, errs
+
+
+@pytest.mark.parametrize("name", F.EDGE_STARTS)
+def test_limiter_ties_against_the_reference(name, fp64_default):
+    """Degenerate starts (w == 0, d == 0 exactly on 16-100 % of the faces): explicit terms, 1 and 3 RK4 steps."""
+    g = load_golden("fvm_edges.npz")
+    ph = F.Physics.of_golden(g, "a1")
+    eq, dt = ph.equation(_rk4()), float(g["a1_dt"])
+    u0 = _dev(g[f"a1_{name}_u0"])
+    with torch.no_grad():
+        k = eq.explicit_terms(u0, dt)
+        u1 = eq(u0, dt)
+        u3 = eq(u0, dt, steps=3)
+    assert _finite(k) and _finite(u1) and _finite(u3)
+    assert rel_l2(_cpu(k), g[f"a1_{name}_explicit"]) <= 1e-12
+    assert rel_l2(_cpu(u1), g[f"a1_{name}_classic_rk4_1"]) <= 1e-11
+    assert rel_l2(_cpu(u3), g[f"a1_{name}_classic_rk4_3"]) <= 1e-11
+    if name == "rest":   # the forcing is sin(k y) e_x: nothing ever drives uy, and ux stays a function of y alone
+        assert torch.equal(u3[1], torch.zeros_like(u3[1]))
+        assert torch.equal(u3[0], u3[0][:1].expand_as(u3[0]))
+
+
+@pytest.mark.parametrize("n", [8, 32, 80, 96])
+@pytest.mark.parametrize("name", F.EDGE_STARTS)
+def test_limiter_ties_at_other_sizes_against_the_restatement(name, n, fp64_default):
+    ph = F.Physics(n)
+    eq, dt = ph.equation(_rk4()), 0.25 * ph.h
+    u0 = _dev(F.degenerate_start(name, n, seed=n))
+    a, b = eq.solver.weights(dt)
+    with torch.no_grad():
+        k = eq.explicit_terms(u0, dt)
+        u3 = eq(u0, dt, steps=3)
+        ok, errs = _band_ok(k, ph.explicit(dt, DEV)(u0), n, 1e-12)
+        assert _finite(k) and ok, errs
+        ok, errs = _band_ok(u3, ph.rollout(a, b, dt, 3, DEV)(u0), n, 1e-11)
+        assert _finite(u3) and ok, errs
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_every_size_family_against_the_restatement(n, fp64_default):
+    """Smooth start, batch 2: explicit terms, projection (of a field that is not divergence free) and 3 RK4 steps."""
+    import torch_cfd_amd as tc
+
+    ph = F.Physics(n, wave=4)
+    eq = ph.equation(_rk4())
+    dt = tc.stable_time_step(dx=ph.h, max_velocity=2.0, max_courant_number=0.5, viscosity=ph.nu)
+    u0 = _smooth(ph, [3, 5])
+    raw = _dev(F.cotangent((2, 2, n, n), n))
+    a, b = eq.solver.weights(dt)
+    with torch.no_grad():
+        ok, errs = _band_ok(eq.explicit_terms(u0, dt), ph.explicit(dt, DEV)(u0), n, 1e-12)
+        assert ok, ("explicit terms", errs)
+        p = eq.pressure_projection(raw)
+        ok, errs = _band_ok(p, ph.projection(DEV)(raw), n, 1e-12)
+        assert ok, ("projection", errs)
+        ok, errs = _band_ok(eq(u0, dt, steps=3), ph.rollout(a, b, dt, 3, DEV)(u0), n, 1e-11)
+        assert ok, ("3 steps", errs)
+    if n in (80, 96):
+        div = (p[0] - torch.roll(p[0], 1, -2)) / ph.h + (p[1] - torch.roll(p[1], 1, -1)) / ph.h
+        umax = torch.maximum(p[0].abs().max(), p[1].abs().max())
+        assert div.abs().max().item() <= 1e-10 * umax.item() / ph.h
+
+
+@pytest.mark.parametrize("tag", F.OPTIONAL_TERMS)
+def test_optional_terms_against_the_reference(tag, fp64_default):
+    """No forcing (a null table) and no drag; density 2 on [0, 1]^2; a negative drag, which is no drag as in the reference."""
+    g = load_golden("fvm_edges.npz")
+    ph = F.Physics.of_golden(g, f"a2_{tag}")
+    eq, dt = ph.equation(_rk4()), float(g[f"a2_{tag}_dt"])
+    u0 = _dev(g[f"a2_{tag}_u0"])
+    with torch.no_grad():
+        assert rel_l2(_cpu(eq.explicit_terms(u0, dt)), g[f"a2_{tag}_explicit"]) <= 1e-12
+        assert rel_l2(_cpu(eq(u0, dt, steps=3)), g[f"a2_{tag}_classic_rk4_3"]) <= 1e-11
+
+
+@pytest.mark.parametrize("name", list(F.TABLEAUX))
+def test_general_tableaux_against_the_reference(name, fp64_default):
+    """Stage states summed from two earlier stages, negative weights, a stage whose row is all zeros."""
+    import torch_cfd_amd as tc
+
+    g = load_golden("fvm_edges.npz")
+    ph = F.Physics.of_golden(g, "a3")
+    eq, dt = ph.equation(tc.RKStepper(tableau=F.TABLEAUX[name], dtype=torch.float64)), float(g["a3_dt"])
+    u0 = _dev(g["a3_u0"])
+    with torch.no_grad():
+        u1 = eq(u0, dt)
+        u3 = eq(u0, dt, steps=3)
+        assert rel_l2(_cpu(u1), g[f"a3_{name}_1"]) <= 1e-11
+        assert rel_l2(_cpu(u3), g[f"a3_{name}_3"]) <= 1e-11
+        if name == "zero_row":
+            u = u1
+            for _ in range(2):
+                u = eq(u, dt)
+            assert torch.equal(u3[0], u[0]) and torch.equal(u3[1], u[1])
+
+
+@pytest.mark.parametrize("case", list(F.OPTIONAL_TERMS) + list(F.TABLEAUX))
+def test_optional_terms_and_tableaux_at_n80_batch_three_against_the_restatement(case, fp64_default):
+    import torch_cfd_amd as tc
+
+    g = load_golden("fvm_edges.npz")
+    if case in F.TABLEAUX:
+        ph, solver = F.Physics.of_golden(g, "a3", n=80), tc.RKStepper(tableau=F.TABLEAUX[case], dtype=torch.float64)
+    else:
+        ph, solver = F.Physics.of_golden(g, f"a2_{case}", n=80), _rk4()
+    eq, dt = ph.equation(solver), 0.25 * ph.h
+    u0 = _smooth(ph, [0, 1, 2])
+    a, b = solver.weights(dt)
+    with torch.no_grad():
+        ok, errs = _band_ok(eq.explicit_terms(u0, dt), ph.explicit(dt, DEV)(u0), 80, 1e-12)
+        assert ok, ("explicit terms", errs)
+        ok, errs = _band_ok(eq(u0, dt, steps=3), ph.rollout(a, b, dt, 3, DEV)(u0), 80, 1e-11)
+        assert ok, ("3 steps", errs)
+
+
+@pytest.mark.parametrize("n", [512, 1024])
+def test_fp32_at_the_large_transforms_within_twice_the_torch_ops_fp32_error(n, fp64_default):
+    """fp32 fields at the sizes whose transforms are the 8-column cross-lane tiles (1024: the cross-lane row kernel too).
+    Truth: the restatement in fp64 on the same fp32 inputs cast up.  Yardstick: the restatement in float32 torch ops on the
+    same device; the kernels may err at most twice as much (two fp32 pipelines order their sums differently).
+    Measured on an MI355X, kernels / torch ops fp32 (rel-L2 for the step and the projection, max|div| h / max|u|):
+        n = 512:   one RK4 step 5.54e-8 / 5.56e-8,  projection 4.46e-7 / 4.51e-7,  divergence 1.14e-6 / 1.10e-6
+        n = 1024:  one RK4 step 5.79e-8 / 5.79e-8,  projection 4.91e-7 / 4.92e-7,  divergence 1.32e-6 / 1.27e-6"""
+    import torch_cfd_amd as tc
+
+    ph = F.Physics(n, wave=4)
+    eq = ph.equation(_rk4())
+    dt = tc.stable_time_step(dx=ph.h, max_velocity=2.0, max_courant_number=0.5, viscosity=ph.nu)
+    a, b = eq.solver.weights(dt)
+    u32 = _smooth(ph, [3, 5], torch.float32)
+    raw32 = _dev(F.cotangent((2, 2, n, n), n), torch.float32)
+    up = lambda u: tuple(c.double() for c in u)   # noqa: E731
+    with torch.no_grad():
+        got = eq(u32, dt)
+        assert got[0].dtype == torch.float32
+        exact = torch.stack(ph.rollout(a, b, dt, 1, DEV)(up(u32))).cpu()
+        ops = torch.stack(ph.rollout(a, b, dt, 1, DEV, torch.float32)(u32)).cpu()
+        assert ops.dtype == torch.float32
+        err, spread = rel_l2(torch.stack(got).cpu(), exact), rel_l2(ops, exact)
+        print(f"fp32 n={n} one RK4 step: kernels {err:.3e}, torch ops fp32 {spread:.3e}")
+        assert err <= 2 * spread, ("step", err, spread)
+
+        p = eq.pressure_projection(raw32)
+        assert p[0].dtype == torch.float32
+        exact = torch.stack(ph.projection(DEV)(up(raw32))).cpu()
+        pops = ph.projection(DEV, torch.float32)(raw32)
+        err, spread = rel_l2(torch.stack(p).cpu(), exact), rel_l2(torch.stack(pops).cpu(), exact)
+        print(f"fp32 n={n} projection: kernels {err:.3e}, torch ops fp32 {spread:.3e}")
+        assert err <= 2 * spread, ("projection", err, spread)
+
+        def divergence(v):   # max|div| h / max|u| of an fp32 field, measured in fp64
+            x, y = up(v)
+            div = (x - torch.roll(x, 1, -2)) / ph.h + (y - torch.roll(y, 1, -1)) / ph.h
+            return div.abs().max().item() * ph.h / max(x.abs().max().item(), y.abs().max().item())
+        err, spread = divergence(p), divergence(pops)
+        print(f"fp32 n={n} divergence after projection: kernels {err:.3e}, torch ops fp32 {spread:.3e}")
+        assert err <= 2 * spread, ("divergence", err, spread)
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+@pytest.mark.parametrize("n, batch", [(32, 17), (80, 9)])
+def test_a_sample_in_a_ragged_batch_evolves_as_it_does_alone(n, batch, dtype, fp64_default):
+    ph = F.Physics(n, wave=4)
+    eq, dt = ph.equation(_rk4()), 0.25 * ph.h
+    u0 = _smooth(ph, range(batch), dtype)
+    with torch.no_grad():
+        out = eq(u0, dt, steps=3)
+        assert out[0].dtype == dtype and out[0].shape == (batch, n, n)
+        for s in (0, 8, batch - 1):
+            alone = eq((u0[0][s].contiguous(), u0[1][s].contiguous()), dt, steps=3)
+            assert torch.equal(out[0][s], alone[0]) and torch.equal(out[1][s], alone[1]), s
+
+
+@pytest.mark.parametrize("n", [100, 48])
+def test_sizes_the_transforms_do_not_hold_raise_naming_the_size(n, fp64_default):
+    """Even sizes the reference accepts and the transforms do not hold: an error that names n, not a crash or values."""
+    import torch_cfd_amd as tc
+
+    ph = F.Physics(n)
+    u = tuple(torch.zeros(n, n, device=DEV) for _ in range(2))
+    eq = ph.equation(_rk4())
+    for call in (lambda: eq(u, 0.01), lambda: eq.explicit_terms(u, 0.01), lambda: eq.pressure_projection(u),
+                 lambda: tc.PressureProjection(ph.grid())(u)):
+        with pytest.raises(tc._lib.TcfdError, match=f"n={n}"):
+            call()

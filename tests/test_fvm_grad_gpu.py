@@ -247,3 +247,150 @@ def test_requires_grad_tableau_still_raises_with_a_differentiable_state(fp64_def
     s = tc.RKStepper.from_method(method="classic_rk4", requires_grad=True)
     with pytest.raises(NotImplementedError):
         s.forward(_leaves(g["n16_b2_u0"]), float(g["n16_b2_dt"]), equation=eq)
+
+
+# ----------------------------------------------------------------------------- the edges: limiter ties, every size family,
+# optional terms, general tableaux, batch independence
+SIZES = (8, 16, 32, 80, 96, 128, 160, 192)   # every size family; at n = 8 the adjoint's stencil (i +- 3) wraps at its limit
+
+
+def _stepper(method="classic_rk4"):
+    import torch_cfd_amd as tc
+
+    return tc.RKStepper.from_method(method=method)
+
+
+def _smooth_leaves(ph, seeds):
+    from torch_cfd_amd import initial_conditions as ic
+
+    ux, uy = ic.filtered_velocity_field(ph.grid(), 2.0, 3.0, random_state=0, device=DEV, batch_seeds=list(seeds))
+    return ux.detach().clone().requires_grad_(), uy.detach().clone().requires_grad_()
+
+
+def _band_err(got, want, n):
+    """rel-L2 of the whole field and, where the last 64-wide x-block is partly masked, of its columns alone."""
+    got, want = got.cpu(), want.cpu()
+    errs = [rel_l2(got, want)]
+    if n > 64 and n % 64:
+        errs.append(rel_l2(got[..., :, 64:], want[..., :, 64:]))
+    return max(errs)
+
+
+@pytest.mark.parametrize("name", F.EDGE_STARTS)
+def test_limiter_tie_vjps_against_the_reference(name, fp64_default):
+    """Degenerate starts: the VJPs of the explicit terms and of one forward Euler step, whose explicit terms see the exact
+    input.  Only here does w > 0 differ from w >= 0 (the flux is ci * w, its w-derivative is ci = clow + ...) and the
+    d == 0 arm of safe_div carry no gradient."""
+    g = load_golden("fvm_edges.npz")
+    ph = F.Physics.of_golden(g, "a1")
+    dt = float(g["a1_dt"])
+    eq = ph.equation(_stepper("forward_euler"))
+    cot = g[f"a1_{name}_cot"]
+    got = _vjp(lambda u: eq.explicit_terms(u, dt), _leaves(g[f"a1_{name}_u0"]), cot)
+    assert torch.isfinite(got).all()
+    err = rel_l2(got.cpu(), g[f"a1_{name}_explicit_vjp"])
+    print(f"{name}: explicit-terms VJP rel-L2 {err:.2e}")
+    assert err <= FP64_BOUND, err
+    got = _vjp(lambda u: eq(u, dt), _leaves(g[f"a1_{name}_u0"]), cot)
+    assert torch.isfinite(got).all()
+    err = rel_l2(got.cpu(), g[f"a1_{name}_forward_euler_vjp"])
+    print(f"{name}: forward-Euler-step VJP rel-L2 {err:.2e}")
+    assert err <= FP64_BOUND, err
+
+
+@pytest.mark.parametrize("n", [8, 32, 80, 96])
+@pytest.mark.parametrize("name", F.EDGE_STARTS)
+def test_limiter_tie_vjps_at_other_sizes_against_the_restatement(name, n, fp64_default):
+    ph = F.Physics(n)
+    dt = 0.25 * ph.h
+    eq = ph.equation(_stepper("forward_euler"))
+    a, b = eq.solver.weights(dt)
+    start = F.degenerate_start(name, n, seed=n)
+    cot = F.cotangent((2, n, n), 7 * n)
+    got = _vjp(lambda u: eq.explicit_terms(u, dt), _leaves(start), cot)
+    want = _vjp(ph.explicit(dt, DEV), _leaves(start), cot)
+    assert torch.isfinite(got).all()
+    assert _band_err(got, want, n) <= FP64_BOUND
+    got = _vjp(lambda u: eq(u, dt), _leaves(start), cot)
+    want = _vjp(ph.rollout(a, b, dt, 1, DEV), _leaves(start), cot)
+    assert torch.isfinite(got).all()
+    assert _band_err(got, want, n) <= FP64_BOUND
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_every_size_family_vjps_against_the_restatement(n, fp64_default):
+    """Smooth start, batch 2: the VJPs of the explicit terms, the projection and 3 RK4 steps."""
+    import torch_cfd_amd as tc
+
+    ph = F.Physics(n, wave=4)
+    eq = ph.equation(_stepper())
+    dt = tc.stable_time_step(dx=ph.h, max_velocity=2.0, max_courant_number=0.5, viscosity=ph.nu)
+    a, b = eq.solver.weights(dt)
+    u = _smooth_leaves(ph, [3, 5])
+    cot = F.cotangent((2, 2, n, n), n)
+    for what, fn, ops in (("explicit terms", lambda v: eq.explicit_terms(v, dt), ph.explicit(dt, DEV)),
+                          ("projection", lambda v: eq.pressure_projection(v), ph.projection(DEV)),
+                          ("3 steps", lambda v: eq(v, dt, steps=3), ph.rollout(a, b, dt, 3, DEV))):
+        err = _band_err(_vjp(fn, u, cot), _vjp(ops, u, cot), n)
+        print(f"n={n} {what}: VJP rel-L2 {err:.2e}")
+        assert err <= FP64_BOUND, (what, err)
+
+
+@pytest.mark.parametrize("tag", F.OPTIONAL_TERMS)
+def test_optional_terms_gradient_against_the_reference(tag, fp64_default):
+    g = load_golden("fvm_edges.npz")
+    ph = F.Physics.of_golden(g, f"a2_{tag}")
+    eq, dt = ph.equation(_stepper()), float(g[f"a2_{tag}_dt"])
+    got = _vjp(lambda u: eq(u, dt, steps=3), _leaves(g[f"a2_{tag}_u0"]), g[f"a2_{tag}_cot"])
+    err = rel_l2(got.cpu(), g[f"a2_{tag}_classic_rk4_3_vjp"])
+    print(f"{tag}: 3-step VJP rel-L2 {err:.2e}")
+    assert err <= FP64_BOUND, err
+
+
+@pytest.mark.parametrize("name", list(F.TABLEAUX))
+def test_general_tableaux_gradient_against_the_reference(name, fp64_default):
+    import torch_cfd_amd as tc
+
+    g = load_golden("fvm_edges.npz")
+    ph = F.Physics.of_golden(g, "a3")
+    eq, dt = ph.equation(tc.RKStepper(tableau=F.TABLEAUX[name], dtype=torch.float64)), float(g["a3_dt"])
+    got = _vjp(lambda u: eq(u, dt, steps=3), _leaves(g["a3_u0"]), g["a3_cot"])
+    err = rel_l2(got.cpu(), g[f"a3_{name}_3_vjp"])
+    print(f"{name}: 3-step VJP rel-L2 {err:.2e}")
+    assert err <= FP64_BOUND, err
+    if name == "zero_row":
+        def chained(u):
+            for _ in range(3):
+                u = eq(u, dt)
+            return u
+        assert torch.equal(got, _vjp(chained, _leaves(g["a3_u0"]), g["a3_cot"]))
+
+
+@pytest.mark.parametrize("case", list(F.OPTIONAL_TERMS) + list(F.TABLEAUX))
+def test_optional_terms_and_tableaux_gradient_at_n80_batch_three_against_the_restatement(case, fp64_default):
+    import torch_cfd_amd as tc
+
+    g = load_golden("fvm_edges.npz")
+    if case in F.TABLEAUX:
+        ph, solver = F.Physics.of_golden(g, "a3", n=80), tc.RKStepper(tableau=F.TABLEAUX[case], dtype=torch.float64)
+    else:
+        ph, solver = F.Physics.of_golden(g, f"a2_{case}", n=80), _stepper()
+    eq, dt = ph.equation(solver), 0.25 * ph.h
+    a, b = solver.weights(dt)
+    u = _smooth_leaves(ph, [0, 1, 2])
+    cot = F.cotangent((3, 2, 80, 80), 80)
+    err = _band_err(_vjp(lambda v: eq(v, dt, steps=3), u, cot), _vjp(ph.rollout(a, b, dt, 3, DEV), u, cot), 80)
+    print(f"{case} at 80^2 x 3: 3-step VJP rel-L2 {err:.2e}")
+    assert err <= FP64_BOUND, err
+
+
+@pytest.mark.parametrize("n, batch", [(32, 17), (80, 9)])
+def test_gradient_of_a_sample_in_a_ragged_batch_is_that_of_the_sample_alone(n, batch, fp64_default):
+    ph = F.Physics(n, wave=4)
+    eq, dt = ph.equation(_stepper()), 0.25 * ph.h
+    u = _smooth_leaves(ph, range(batch))
+    cot = F.cotangent((batch, 2, n, n), batch)
+    got = _vjp(lambda v: eq(v, dt, steps=3), u, cot)
+    for s in (0, 8, batch - 1):
+        alone = (u[0][s].detach().clone().requires_grad_(), u[1][s].detach().clone().requires_grad_())
+        assert torch.equal(got[s], _vjp(lambda v: eq(v, dt, steps=3), alone, cot[s])), s

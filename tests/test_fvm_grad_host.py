@@ -141,3 +141,50 @@ def test_default_tableau_does_not_block_the_velocity_gradient():
     u = (torch.zeros(32, 32, requires_grad=True), torch.zeros(32, 32, requires_grad=True))
     with pytest.raises(tc._lib.TcfdError):
         eq(u, 0.01)
+
+
+# ----------------------------------------------------------------------------- the edges (tests/golden/fvm_edges.npz)
+def _edge_vjp(fn, a, cot):
+    return _vjp(lambda x, y: fn((x, y)), _leaves(a), cot)
+
+
+@pytest.mark.parametrize("name", F.EDGE_STARTS)
+def test_restatement_vjps_at_the_limiter_ties_against_the_reference(name):
+    """Explicit terms and one forward Euler step: both see the exact input, so the ties are exact on both sides."""
+    import torch_cfd_amd as tc
+
+    g = load_golden("fvm_edges.npz")
+    ph = F.Physics.of_golden(g, "a1")
+    dt = float(g["a1_dt"])
+    u0, cot = g[f"a1_{name}_u0"], g[f"a1_{name}_cot"]
+    got = _edge_vjp(ph.explicit(dt), u0, cot)
+    assert torch.isfinite(got).all()
+    assert rel_l2(got, g[f"a1_{name}_explicit_vjp"]) <= 1e-13
+    a, b = tc.RKStepper.from_method(method="forward_euler").weights(dt)
+    got = _edge_vjp(ph.rollout(a, b, dt, 1), u0, cot)
+    assert torch.isfinite(got).all()
+    assert rel_l2(got, g[f"a1_{name}_forward_euler_vjp"]) <= 1e-12
+
+
+@pytest.mark.parametrize("tag", F.OPTIONAL_TERMS)
+def test_restatement_optional_terms_gradient_against_the_reference(tag):
+    import torch_cfd_amd as tc
+
+    g = load_golden("fvm_edges.npz")
+    ph = F.Physics.of_golden(g, f"a2_{tag}")
+    dt = float(g[f"a2_{tag}_dt"])
+    a, b = tc.RKStepper.from_method(method="classic_rk4").weights(dt)
+    got = _edge_vjp(ph.rollout(a, b, dt, 3), g[f"a2_{tag}_u0"], g[f"a2_{tag}_cot"])
+    assert rel_l2(got, g[f"a2_{tag}_classic_rk4_3_vjp"]) <= 1e-12
+
+
+@pytest.mark.parametrize("name", list(F.TABLEAUX))
+def test_restatement_general_tableaux_gradient_against_the_reference(name):
+    import torch_cfd_amd as tc
+
+    g = load_golden("fvm_edges.npz")
+    ph = F.Physics.of_golden(g, "a3")
+    dt = float(g["a3_dt"])
+    a, b = tc.RKStepper(tableau=F.TABLEAUX[name], dtype=torch.float64).weights(dt)
+    got = _edge_vjp(ph.rollout(a, b, dt, 3), g["a3_u0"], g["a3_cot"])
+    assert rel_l2(got, g[f"a3_{name}_3_vjp"]) <= 1e-12

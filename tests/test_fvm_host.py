@@ -172,3 +172,85 @@ def test_restatement_steps_against_the_reference(method):
         if s == 0:
             assert rel_l2(torch.stack((ux, uy)), load_golden("fvm_small_s0.npz")[f"{method}_1"]) <= 1e-13
     assert rel_l2(torch.stack((ux, uy)), load_golden("fvm_small_s0.npz")[f"{method}_10"]) <= 1e-12
+
+
+# ----------------------------------------------------------------------------- the edges (tests/golden/fvm_edges.npz)
+def _edges():
+    return load_golden("fvm_edges.npz")
+
+
+def _pair(a):
+    t = torch.from_numpy(np.asarray(a))
+    return t[..., 0, :, :], t[..., 1, :, :]
+
+
+def _weights(tableau, dt):
+    import torch_cfd_amd as tc
+
+    return tc.RKStepper(tableau=tableau, dtype=torch.float64).weights(dt)
+
+
+def test_edge_inputs_are_the_shared_families():
+    """The golden's degenerate starts and tableaux are the ones tests/fvm_ops.py hands the GPU tests at other sizes."""
+    g = _edges()
+    assert [str(s) for s in g["starts"]] == list(F.EDGE_STARTS)
+    for si, name in enumerate(F.EDGE_STARTS):
+        assert torch.equal(F.degenerate_start(name, int(g["n"]), seed=100 + si), torch.from_numpy(g[f"a1_{name}_u0"]))
+    for name, tableau in F.TABLEAUX.items():
+        a, b = _weights(tableau, 1.0)
+        assert a == g[f"a3_{name}_a"].reshape(-1).tolist() and b == g[f"a3_{name}_b"].tolist()
+
+
+@pytest.mark.parametrize("name", F.EDGE_STARTS)
+def test_degenerate_starts_sit_on_the_limiter_ties(name):
+    """Every family has exact ties on a large share of its faces: w == 0 and d == 0 (rest: all of them)."""
+    for n in (8, 16, 32, 80, 96):
+        ux, uy = F.degenerate_start(name, n, seed=n)
+        w = 0.5 * ux + 0.5 * torch.roll(ux, -1, -2)
+        d = torch.roll(ux, -1, -2) - ux
+        assert (w == 0).double().mean().item() >= 0.15, (name, n)
+        if name != "checker":   # the checkerboard is the w == 0, d != 0 family
+            assert (d == 0).double().mean().item() >= 0.15, (name, n)
+        else:
+            assert (d != 0).all() and (w == 0).all()
+
+
+@pytest.mark.parametrize("name", F.EDGE_STARTS)
+def test_restatement_at_the_limiter_ties_against_the_reference(name):
+    import torch_cfd_amd as tc
+
+    g = _edges()
+    ph = F.Physics.of_golden(g, "a1")
+    dt = float(g["a1_dt"])
+    u0 = _pair(g[f"a1_{name}_u0"])
+    assert rel_l2(torch.stack(ph.explicit(dt)(u0)), g[f"a1_{name}_explicit"]) <= 1e-13
+    a, b = tc.RKStepper.from_method(method="classic_rk4").weights(dt)
+    assert rel_l2(torch.stack(ph.rollout(a, b, dt, 1)(u0)), g[f"a1_{name}_classic_rk4_1"]) <= 1e-13
+    assert rel_l2(torch.stack(ph.rollout(a, b, dt, 3)(u0)), g[f"a1_{name}_classic_rk4_3"]) <= 1e-12
+
+
+@pytest.mark.parametrize("tag", F.OPTIONAL_TERMS)
+def test_restatement_optional_terms_against_the_reference(tag):
+    """No forcing and no drag; density 2 on [0, 1]^2 (nu / density, force / density, h = 1 / n); a negative drag, which is
+    no drag (the reference applies the term only for drag > 0)."""
+    import torch_cfd_amd as tc
+
+    g = _edges()
+    ph = F.Physics.of_golden(g, f"a2_{tag}")
+    assert ph.drag <= 0 and (ph.wave is None) == (tag != "dense") and ph.density == (2.0 if tag == "dense" else 1.0)
+    dt = float(g[f"a2_{tag}_dt"])
+    u0 = _pair(g[f"a2_{tag}_u0"])
+    assert rel_l2(torch.stack(ph.explicit(dt)(u0)), g[f"a2_{tag}_explicit"]) <= 1e-13
+    a, b = tc.RKStepper.from_method(method="classic_rk4").weights(dt)
+    assert rel_l2(torch.stack(ph.rollout(a, b, dt, 3)(u0)), g[f"a2_{tag}_classic_rk4_3"]) <= 1e-12
+
+
+@pytest.mark.parametrize("name", list(F.TABLEAUX))
+def test_restatement_general_tableaux_against_the_reference(name):
+    g = _edges()
+    ph = F.Physics.of_golden(g, "a3")
+    dt = float(g["a3_dt"])
+    a, b = _weights(F.TABLEAUX[name], dt)
+    u0 = _pair(g["a3_u0"])
+    assert rel_l2(torch.stack(ph.rollout(a, b, dt, 1)(u0)), g[f"a3_{name}_1"]) <= 1e-13
+    assert rel_l2(torch.stack(ph.rollout(a, b, dt, 3)(u0)), g[f"a3_{name}_3"]) <= 1e-12
