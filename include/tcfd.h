@@ -56,7 +56,7 @@ typedef struct tcfd_ns2d_plan tcfd_ns2d_plan;
 typedef struct tcfd_fno_plan tcfd_fno_plan;
 typedef struct tcfd_fvm_plan tcfd_fvm_plan;
 
-#define TCFD_ABI_VERSION 12  /* what tcfd_version() of a library built from THIS header returns */
+#define TCFD_ABI_VERSION 13  /* what tcfd_version() of a library built from THIS header returns */
 
 #ifndef TCFD_H_TYPES_ONLY   /* (the library's second compilation unit wants the types without the prototypes) */
 
@@ -68,7 +68,8 @@ const char* tcfd_last_error(void);
  * 8: tcfd_fvm_*; 9: tcfd_fvm_explicit_terms_vjp, tcfd_fvm_step_vjp_workspace_bytes, tcfd_fvm_step_vjp; 10: tcfd_ns2d_refine,
  * tcfd_ns2d_refine_vjp, tcfd_ns2d_refine_workspace_bytes; 11: tcfd_grf_spectrum, tcfd_grf_spectrum_workspace_bytes;
  * 12: tcfd_residual_loss, tcfd_residual_loss_backward, tcfd_residual_loss_supported, tcfd_residual_workspace_bytes, tcfd_lp_sums,
- * tcfd_lp_sums_bwd, tcfd_lp_sums_workspace_bytes, tcfd_h1_sums, tcfd_h1_sums_bwd, tcfd_h1_sums_workspace_bytes).  A host compares it with the TCFD_ABI_VERSION it was written against BEFORE the
+ * tcfd_lp_sums_bwd, tcfd_lp_sums_workspace_bytes, tcfd_h1_sums, tcfd_h1_sums_bwd, tcfd_h1_sums_workspace_bytes;
+ * 13: tcfd_fvm_plan_set_advection and the TCFD_FVM_* advection schemes; no earlier entry point changed).  A host compares it with the TCFD_ABI_VERSION it was written against BEFORE the
  * first call: a stale prebuilt library would otherwise be called with the wrong argument layout and return garbage
  * (torch-cfd_amd/_lib.py::load does). */
 int tcfd_version(void);
@@ -576,6 +577,18 @@ int tcfd_fvm_project(const tcfd_fvm_plan* plan, const void* ux, const void* uy, 
 int tcfd_fvm_step(const tcfd_fvm_plan* plan, const void* ux_in, const void* uy_in, void* ux_out, void* uy_out, long batch,
                   int steps, int nstages, const double* a, const double* b, double dt, void* workspace,
                   size_t workspace_bytes, void* stream);
+
+/* Advection scheme of a plan: the interpolation of the transported component to the faces of its control volume
+ * (torch_cfd/interpolation.py; the face velocity is always the linear interpolation).  A fresh plan is TCFD_FVM_VAN_LEER.
+ * Every call that evaluates the explicit terms or their adjoint (explicit_terms, step, explicit_terms_vjp, step_vjp) reads
+ * the scheme when it launches.  An unknown value returns TCFD_EINVAL, names it in tcfd_last_error and leaves the plan as it was. */
+enum {
+    TCFD_FVM_VAN_LEER = 0,     /* apply_tvd_limiter(lax_wendroff, van_leer_limiter): the reference's convect */
+    TCFD_FVM_UPWIND = 1,       /* upwind: the value on the side the face velocity comes from (w > 0: the lower cell) */
+    TCFD_FVM_LINEAR = 2,       /* linear: the mean of the two cells (central differences; not TVD) */
+    TCFD_FVM_LAX_WENDROFF = 3  /* lax_wendroff: the unlimited second-order interpolation (not TVD) */
+};
+int tcfd_fvm_plan_set_advection(tcfd_fvm_plan* plan, int scheme);
 
 /* Vector-Jacobian products of the finite-volume solver (reverse mode; the projection is symmetric, so tcfd_fvm_project of a
  * cotangent is its own VJP).  The derivatives follow the branches torch autograd takes through the reference's ops.

@@ -21,6 +21,8 @@ from .forcings import FieldArray, ForcingFn, KolmogorovForcing, SimpleSolenoidal
 from .solvers import get_trajectory_imex  # noqa: F401
 from .grf import GRF2d  # noqa: F401
 from .fvm import NavierStokes2DFVMProjection, PressureProjection, RKStepper, get_trajectory_fvm  # noqa: F401
+from . import fvm, interpolation  # noqa: F401  (fvm.advection / fvm.convect and the scheme descriptors)
+from .fvm import advection  # noqa: F401
 from .spectral import (  # noqa: F401
     brick_wall_filter_2d,
     fft_mesh_2d,

@@ -28,7 +28,9 @@ SOURCES = ("tcfd_ns2d.hip", "tcfd_fno.hip", "tcfd_fno_pw.hip", "tcfd_fno_tiles.h
            "tcfd_grf.hip", "tcfd_residual.hip")
 
 TCFD_C64, TCFD_C128 = 0, 1
-ABI_VERSION = 12  # TCFD_ABI_VERSION of include/tcfd.h the SIGNATURES table below was written against
+# advection schemes of a finite-volume plan (include/tcfd.h TCFD_FVM_*)
+TCFD_FVM_VAN_LEER, TCFD_FVM_UPWIND, TCFD_FVM_LINEAR, TCFD_FVM_LAX_WENDROFF = 0, 1, 2, 3
+ABI_VERSION = 13  # TCFD_ABI_VERSION of include/tcfd.h the SIGNATURES table below was written against
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -202,6 +204,7 @@ SIGNATURES = {
     "tcfd_host_unregister": (_i, [_vp]),
     "tcfd_fvm_plan_create": (_i, [ctypes.POINTER(_vp), _i, _i, _d, _d, _d, _dp, _dp, _dp]),
     "tcfd_fvm_plan_destroy": (None, [_vp]),
+    "tcfd_fvm_plan_set_advection": (_i, [_vp, _i]),
     "tcfd_fvm_workspace_bytes": (_sz, [_vp, _l]),
     "tcfd_fvm_explicit_terms": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _d, _vp]),
     "tcfd_fvm_project": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _vp, _sz, _vp]),

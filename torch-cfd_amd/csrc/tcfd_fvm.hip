@@ -8,6 +8,7 @@
 // Launch sequence of one RK stage i (TCFD_UNIT 0 = fp64, 1 = fp32 instantiations):
 //   k_fvm_apply    u_i = u*_i - grad q_i (forward differences of q; skipped for stage 0, whose state is u0)
 //   k_fvm_stage    k_i = explicit_terms(u_i) in registers; u*_m (+)= c_mi k_i for every later stage m and the final sum
+//                  (one instantiation per advection scheme of the plan, chosen by a host-side switch at launch)
 //   k_fvm_div      backward-difference divergence of the next u*
 //   tcfd_rfft2 -> k_fvm_mul (x inverse eigenvalues) -> tcfd_irfft2: q of the next stage
 // The transforms are the spectral solver's kernels (tcfd_ns2d.hip) on a table-free plan held by the FVM plan.
@@ -92,49 +93,50 @@ __device__ __forceinline__ T tvd_flux(T cm, T c0, T c1, T c2, T w, T cfl) {
 template <typename T>
 __device__ __forceinline__ T half(T a, T b) { return T(0.5) * a + T(0.5) * b; }
 
-// explicit_terms of both velocity components at cell (i, j) of field plane X / Y (fvm.py:397-409):
-// ((convect + nu lap) + f) + (-drag) u
-template <typename T>
-__device__ __forceinline__ void explicit_point(const T* __restrict__ X, const T* __restrict__ Y, const T* __restrict__ fx,
-                                               const T* __restrict__ fy, int i, int j, int n, const StageConst<T>& s,
-                                               T& kx, T& ky) {
-    const int im2 = wrap(i - 2, n), im1 = wrap(i - 1, n), ip1 = wrap(i + 1, n), ip2 = wrap(i + 2, n);
-    const int jm2 = wrap(j - 2, n), jm1 = wrap(j - 1, n), jp1 = wrap(j + 1, n), jp2 = wrap(j + 2, n);
-    auto at = [n](const T* p, int a, int b) { return p[(size_t)a * n + b]; };
+// advection scheme of a plan (tcfd.h TCFD_FVM_*): the interpolation of the transported component to a face, a compile-time
+// choice of the stage kernel and of its adjoint.  VAN_LEER reads the four cells cm .. c2 around the face (tvd_flux); the other
+// three read the two cells c0, c1 next to it (face_flux), so their instantiations never form the +-2 neighbours' addresses.
+constexpr int VAN_LEER = TCFD_FVM_VAN_LEER, UPWIND = TCFD_FVM_UPWIND, LINEAR = TCFD_FVM_LINEAR,
+              LAX_WENDROFF = TCFD_FVM_LAX_WENDROFF;
 
-    // ---- ux: control volume centred at its own face, faces at (i + 3/2, j + 1/2) and (i + 1, j + 1)
-    const T x00 = at(X, i, j);
-    const T xm2 = at(X, im2, j), xm1 = at(X, im1, j), xp1 = at(X, ip1, j), xp2 = at(X, ip2, j);
-    const T xjm2 = at(X, i, jm2), xjm1 = at(X, i, jm1), xjp1 = at(X, i, jp1), xjp2 = at(X, i, jp2);
-    const T y00 = at(Y, i, j);
-    const T yp1 = at(Y, ip1, j), yjm1 = at(Y, i, jm1), yp1jm1 = at(Y, ip1, jm1);
-    T adv_x;
-    {
-        const T f_hi = tvd_flux(xm1, x00, xp1, xp2, half(x00, xp1), s.cfl);
-        const T f_lo = tvd_flux(xm2, xm1, x00, xp1, half(xm1, x00), s.cfl);
-        const T g_hi = tvd_flux(xjm1, x00, xjp1, xjp2, half(y00, yp1), s.cfl);
-        const T g_lo = tvd_flux(xjm2, xjm1, x00, xjp1, half(yjm1, yp1jm1), s.cfl);
-        adv_x = -((f_hi - f_lo) / s.h + (g_hi - g_lo) / s.h);
+// flux of the two-cell schemes across the face between c0 and c1, face velocity w:
+//   UPWIND        where(w > 0, c0, c1) * w                                        (interpolation.py:102; w == 0 takes c1)
+//   LINEAR        (0.5 c0 + 0.5 c1) * w                                           (:39, floor and ceil weights at offset 1/2)
+//   LAX_WENDROFF  where(w > 0, c0 + 0.5 (1 - cr) d, c1 - 0.5 (1 + cr) d) * w      (:171; cr = cfl w, d = c1 - c0)
+template <int SCHEME, typename T>
+__device__ __forceinline__ T face_flux(T c0, T c1, T w, T cfl) {
+    static_assert(SCHEME == UPWIND || SCHEME == LINEAR || SCHEME == LAX_WENDROFF, "two-cell schemes only");
+    if constexpr (SCHEME == UPWIND) {
+        return (w > T(0) ? c0 : c1) * w;
+    } else if constexpr (SCHEME == LINEAR) {
+        return half(c0, c1) * w;
+    } else {
+        const T cr = cfl * w;
+        const T d = c1 - c0;
+        const T hp = c0 + (T(0.5) * (T(1) - cr)) * d;
+        const T hn = c1 - (T(0.5) * (T(1) + cr)) * d;
+        return (w > T(0) ? hp : hn) * w;
     }
-    // ---- uy: faces at (i + 1, j + 1) and (i + 1/2, j + 3/2)
-    const T ym2 = at(Y, im2, j), ym1 = at(Y, im1, j), yp2 = at(Y, ip2, j);
-    const T yjm2 = at(Y, i, jm2), yjp1 = at(Y, i, jp1), yjp2 = at(Y, i, jp2);
-    const T xm1jp1 = at(X, im1, jp1);
-    T adv_y;
-    {
-        const T f_hi = tvd_flux(ym1, y00, yp1, yp2, half(x00, xjp1), s.cfl);
-        const T f_lo = tvd_flux(ym2, ym1, y00, yp1, half(xm1, xm1jp1), s.cfl);
-        const T g_hi = tvd_flux(yjm1, y00, yjp1, yjp2, half(y00, yjp1), s.cfl);
-        const T g_lo = tvd_flux(yjm2, yjm1, y00, yjp1, half(yjm1, y00), s.cfl);
-        adv_y = -((f_hi - f_lo) / s.h + (g_hi - g_lo) / s.h);
-    }
+}
+
+// the values both kinds of scheme share: the 5-point stencils of the two components around cell (i, j)
+template <typename T>
+struct Near {
+    T x00, xm1, xp1, xjm1, xjp1, y00, ym1, yp1, yjm1, yjp1;
+};
+
+// ((convect + nu lap) + f) + (-drag) u from the advection terms of cell (i, j) (fvm.py:397-409)
+template <typename T>
+__device__ __forceinline__ void finish_point(const Near<T>& v, T adv_x, T adv_y, const T* __restrict__ fx,
+                                             const T* __restrict__ fy, int i, int j, int n, const StageConst<T>& s, T& kx,
+                                             T& ky) {
     // laplacian (finite_differences.py:150): (-2 u) * sum(scales) + (u[-1] + u[+1]) * s0 + (u[-1] + u[+1]) * s1
-    T lap_x = (T(-2) * x00) * s.sum_s;
-    lap_x = lap_x + (xm1 + xp1) * s.inv_h2;
-    lap_x = lap_x + (xjm1 + xjp1) * s.inv_h2;
-    T lap_y = (T(-2) * y00) * s.sum_s;
-    lap_y = lap_y + (ym1 + yp1) * s.inv_h2;
-    lap_y = lap_y + (yjm1 + yjp1) * s.inv_h2;
+    T lap_x = (T(-2) * v.x00) * s.sum_s;
+    lap_x = lap_x + (v.xm1 + v.xp1) * s.inv_h2;
+    lap_x = lap_x + (v.xjm1 + v.xjp1) * s.inv_h2;
+    T lap_y = (T(-2) * v.y00) * s.sum_s;
+    lap_y = lap_y + (v.ym1 + v.yp1) * s.inv_h2;
+    lap_y = lap_y + (v.yjm1 + v.yjp1) * s.inv_h2;
 
     kx = adv_x + s.nu * lap_x;
     ky = adv_y + s.nu * lap_y;
@@ -144,13 +146,79 @@ __device__ __forceinline__ void explicit_point(const T* __restrict__ X, const T*
         ky = ky + fy[p];
     }
     if (s.drag_on) {
-        kx = kx + x00 * s.neg_drag;
-        ky = ky + y00 * s.neg_drag;
+        kx = kx + v.x00 * s.neg_drag;
+        ky = ky + v.y00 * s.neg_drag;
+    }
+}
+
+// explicit_terms of both velocity components at cell (i, j) of field plane X / Y, the advection by the scheme SCHEME.
+// VAN_LEER reads the -2 .. +2 stencils of both components and two corners, 20 loads; the two-cell schemes the 5-point
+// stencils and the same corners, 12 loads: their branch never forms the +-2 indices.
+template <int SCHEME, typename T>
+__device__ __forceinline__ void explicit_point(const T* __restrict__ X, const T* __restrict__ Y, const T* __restrict__ fx,
+                                               const T* __restrict__ fy, int i, int j, int n, const StageConst<T>& s,
+                                               T& kx, T& ky) {
+    auto at = [n](const T* p, int a, int b) { return p[(size_t)a * n + b]; };
+    if constexpr (SCHEME == VAN_LEER) {
+        const int im2 = wrap(i - 2, n), im1 = wrap(i - 1, n), ip1 = wrap(i + 1, n), ip2 = wrap(i + 2, n);
+        const int jm2 = wrap(j - 2, n), jm1 = wrap(j - 1, n), jp1 = wrap(j + 1, n), jp2 = wrap(j + 2, n);
+
+        // ---- ux: control volume centred at its own face, faces at (i + 3/2, j + 1/2) and (i + 1, j + 1)
+        const T x00 = at(X, i, j);
+        const T xm2 = at(X, im2, j), xm1 = at(X, im1, j), xp1 = at(X, ip1, j), xp2 = at(X, ip2, j);
+        const T xjm2 = at(X, i, jm2), xjm1 = at(X, i, jm1), xjp1 = at(X, i, jp1), xjp2 = at(X, i, jp2);
+        const T y00 = at(Y, i, j);
+        const T yp1 = at(Y, ip1, j), yjm1 = at(Y, i, jm1), yp1jm1 = at(Y, ip1, jm1);
+        T adv_x;
+        {
+            const T f_hi = tvd_flux(xm1, x00, xp1, xp2, half(x00, xp1), s.cfl);
+            const T f_lo = tvd_flux(xm2, xm1, x00, xp1, half(xm1, x00), s.cfl);
+            const T g_hi = tvd_flux(xjm1, x00, xjp1, xjp2, half(y00, yp1), s.cfl);
+            const T g_lo = tvd_flux(xjm2, xjm1, x00, xjp1, half(yjm1, yp1jm1), s.cfl);
+            adv_x = -((f_hi - f_lo) / s.h + (g_hi - g_lo) / s.h);
+        }
+        // ---- uy: faces at (i + 1, j + 1) and (i + 1/2, j + 3/2)
+        const T ym2 = at(Y, im2, j), ym1 = at(Y, im1, j), yp2 = at(Y, ip2, j);
+        const T yjm2 = at(Y, i, jm2), yjp1 = at(Y, i, jp1), yjp2 = at(Y, i, jp2);
+        const T xm1jp1 = at(X, im1, jp1);
+        T adv_y;
+        {
+            const T f_hi = tvd_flux(ym1, y00, yp1, yp2, half(x00, xjp1), s.cfl);
+            const T f_lo = tvd_flux(ym2, ym1, y00, yp1, half(xm1, xm1jp1), s.cfl);
+            const T g_hi = tvd_flux(yjm1, y00, yjp1, yjp2, half(y00, yjp1), s.cfl);
+            const T g_lo = tvd_flux(yjm2, yjm1, y00, yjp1, half(yjm1, y00), s.cfl);
+            adv_y = -((f_hi - f_lo) / s.h + (g_hi - g_lo) / s.h);
+        }
+        finish_point(Near<T>{x00, xm1, xp1, xjm1, xjp1, y00, ym1, yp1, yjm1, yjp1}, adv_x, adv_y, fx, fy, i, j, n, s, kx, ky);
+    } else {
+        const int im1 = wrap(i - 1, n), ip1 = wrap(i + 1, n);
+        const int jm1 = wrap(j - 1, n), jp1 = wrap(j + 1, n);
+        const T x00 = at(X, i, j);
+        const T xm1 = at(X, im1, j), xp1 = at(X, ip1, j), xjm1 = at(X, i, jm1), xjp1 = at(X, i, jp1);
+        const T y00 = at(Y, i, j);
+        const T ym1 = at(Y, im1, j), yp1 = at(Y, ip1, j), yjm1 = at(Y, i, jm1), yjp1 = at(Y, i, jp1);
+        const T yp1jm1 = at(Y, ip1, jm1), xm1jp1 = at(X, im1, jp1);   // the far ends of the lower faces' velocities
+        T adv_x, adv_y;
+        {   // ux: the faces of the van Leer branch, each flux from the two cells next to the face
+            const T f_hi = face_flux<SCHEME>(x00, xp1, half(x00, xp1), s.cfl);
+            const T f_lo = face_flux<SCHEME>(xm1, x00, half(xm1, x00), s.cfl);
+            const T g_hi = face_flux<SCHEME>(x00, xjp1, half(y00, yp1), s.cfl);
+            const T g_lo = face_flux<SCHEME>(xjm1, x00, half(yjm1, yp1jm1), s.cfl);
+            adv_x = -((f_hi - f_lo) / s.h + (g_hi - g_lo) / s.h);
+        }
+        {   // uy
+            const T f_hi = face_flux<SCHEME>(y00, yp1, half(x00, xjp1), s.cfl);
+            const T f_lo = face_flux<SCHEME>(ym1, y00, half(xm1, xm1jp1), s.cfl);
+            const T g_hi = face_flux<SCHEME>(y00, yjp1, half(y00, yjp1), s.cfl);
+            const T g_lo = face_flux<SCHEME>(yjm1, y00, half(yjm1, y00), s.cfl);
+            adv_y = -((f_hi - f_lo) / s.h + (g_hi - g_lo) / s.h);
+        }
+        finish_point(Near<T>{x00, xm1, xp1, xjm1, xjp1, y00, ym1, yp1, yjm1, yjp1}, adv_x, adv_y, fx, fy, i, j, n, s, kx, ky);
     }
 }
 
 // one thread per cell; blockIdx.z = sample
-template <typename T>
+template <int SCHEME, typename T>
 __global__ void __launch_bounds__(256) k_fvm_stage(const T* __restrict__ ux, const T* __restrict__ uy, const T* __restrict__ u0x,
                                                    const T* __restrict__ u0y, const T* __restrict__ fx, const T* __restrict__ fy,
                                                    T* __restrict__ kx_out, T* __restrict__ ky_out, Targets<T> tg, StageConst<T> s,
@@ -161,7 +229,7 @@ __global__ void __launch_bounds__(256) k_fvm_stage(const T* __restrict__ ux, con
     const size_t plane = (size_t)n * n;
     const size_t base = (size_t)blockIdx.z * plane;
     T kx, ky;
-    explicit_point(ux + base, uy + base, fx, fy, i, j, n, s, kx, ky);
+    explicit_point<SCHEME>(ux + base, uy + base, fx, fy, i, j, n, s, kx, ky);
     const size_t p = base + (size_t)i * n + j;
     if (kx_out) {
         kx_out[p] = kx;
@@ -286,6 +354,43 @@ __device__ __forceinline__ FluxBar<T> tvd_flux_vjp(T cm, T c0, T c1, T c2, T w, 
     return g;
 }
 
+// cotangents of the inputs (c0, c1, w) of face_flux, given the cotangent lam of its result, by the same rules: the selection
+// w > 0 passes no gradient (w == 0 takes the c1 branch, as the forward), w enters through the final product and, for
+// LAX_WENDROFF, through the Courant number.
+template <typename T>
+struct FaceBar {
+    T c0, c1, w;
+};
+
+template <int SCHEME, typename T>
+__device__ __forceinline__ FaceBar<T> face_flux_vjp(T c0, T c1, T w, T cfl, T lam) {
+    static_assert(SCHEME == UPWIND || SCHEME == LINEAR || SCHEME == LAX_WENDROFF, "two-cell schemes only");
+    const T bci = lam * w;   // flux = ci w
+    FaceBar<T> g;
+    if constexpr (SCHEME == UPWIND) {
+        const bool pos = w > T(0);
+        g.w = lam * (pos ? c0 : c1);
+        g.c0 = pos ? bci : T(0);
+        g.c1 = pos ? T(0) : bci;
+    } else if constexpr (SCHEME == LINEAR) {
+        g.w = lam * half(c0, c1);
+        g.c0 = bci * T(0.5);
+        g.c1 = bci * T(0.5);
+    } else {
+        const bool pos = w > T(0);
+        const T cr = cfl * w;
+        const T d = c1 - c0;
+        const T alpha = T(0.5) * (T(1) - cr);   // hp = c0 + alpha d
+        const T beta = T(0.5) * (T(1) + cr);    // hn = c1 - beta d
+        const T ci = pos ? c0 + alpha * d : c1 - beta * d;
+        g.w = lam * ci + bci * (T(-0.5) * cfl * d);   // d ci / d w = -cfl d / 2 in both branches
+        const T bd = pos ? bci * alpha : -(bci * beta);
+        g.c0 = (pos ? bci : T(0)) - bd;
+        g.c1 = (pos ? T(0) : bci) + bd;
+    }
+    return g;
+}
+
 // (lx, ly) = J^T (LX, LY) of explicit_point at cell (i, j): X / Y the state, LX / LY the cotangent of (kx, ky).
 // Face fluxes (p, q any cell, all indices periodic):
 //   FX[p][q] ux along axis 0: tvd_flux(X[p-1][q], X[p][q], X[p+1][q], X[p+2][q], half(X[p][q], X[p+1][q]))
@@ -296,52 +401,105 @@ __device__ __forceinline__ FluxBar<T> tvd_flux_vjp(T cm, T c0, T c1, T c2, T w, 
 // (LX[p+1][q] - LX[p][q]) / h, and likewise for the others.  X[i][j] is read by FX[i-2 .. i+1][j], GX[i][j-2 .. j+1] and
 // the face velocities of FY[i][j-1 .. j]; Y[i][j] by FY[i-2 .. i+1][j], GY[i][j-2 .. j+1] and the face velocities of
 // GX[i-1 .. i][j]: 18 flux evaluations per cell, against the forward's 8.
-template <typename T>
+// The two-cell schemes' faces F(c0, c1, w) drop the cm and c2 arguments above: X[i][j] is the c1 of FX[i-1][j] and
+// GX[i][j-1], the c0 of FX[i][j] and GX[i][j], and half of the face velocities of FX[i-1 .. i][j] and FY[i][j-1 .. j];
+// Y[i][j] likewise.  The faces two cells away have identically zero partials and are not evaluated: 10 flux evaluations per
+// cell (FY[i][j] and GX[i][j] serve both components), reading the 5-point stencils of X and Y, the corners (i-1, j+1) and
+// (i+1, j-1) of both, the 5-point stencils of LX and LY, LX[i-1][j+1] and LY[i+1][j-1].
+template <int SCHEME, typename T>
 __device__ __forceinline__ void explicit_point_vjp(const T* __restrict__ X, const T* __restrict__ Y, const T* __restrict__ LX,
                                                    const T* __restrict__ LY, int i, int j, int n, const StageConst<T>& s, T& lx,
                                                    T& ly) {
     auto at = [n](const T* p, int a, int b) { return p[(size_t)wrap(a, n) * n + wrap(b, n)]; };
     auto cot = [&](const T* l, int a, int b, int a1, int b1) { return (at(l, a1, b1) - at(l, a, b)) / s.h; };
     T gx = T(0), gy = T(0);
+    if constexpr (SCHEME == VAN_LEER) {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {   // FX[p][j], p = i - 2 + k: X[i][j] is its c2, c1, c0, cm
-        const int p = i - 2 + k;
-        const T c0 = at(X, p, j), c1 = at(X, p + 1, j);
-        const FluxBar<T> b = tvd_flux_vjp(at(X, p - 1, j), c0, c1, at(X, p + 2, j), half(c0, c1), s.cfl, cot(LX, p, j, p + 1, j));
-        gx = gx + (k == 0 ? b.c2 : k == 1 ? b.c1 + T(0.5) * b.w : k == 2 ? b.c0 + T(0.5) * b.w : b.cm);
-    }
+        for (int k = 0; k < 4; ++k) {   // FX[p][j], p = i - 2 + k: X[i][j] is its c2, c1, c0, cm
+            const int p = i - 2 + k;
+            const T c0 = at(X, p, j), c1 = at(X, p + 1, j);
+            const FluxBar<T> b = tvd_flux_vjp(at(X, p - 1, j), c0, c1, at(X, p + 2, j), half(c0, c1), s.cfl, cot(LX, p, j, p + 1, j));
+            gx = gx + (k == 0 ? b.c2 : k == 1 ? b.c1 + T(0.5) * b.w : k == 2 ? b.c0 + T(0.5) * b.w : b.cm);
+        }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {   // GX[i][q], q = j - 2 + k; Y[i][j] is the first half of the face velocity of GX[i][j]
-        const int q = j - 2 + k;
-        const FluxBar<T> b = tvd_flux_vjp(at(X, i, q - 1), at(X, i, q), at(X, i, q + 1), at(X, i, q + 2),
-                                          half(at(Y, i, q), at(Y, i + 1, q)), s.cfl, cot(LX, i, q, i, q + 1));
-        gx = gx + (k == 0 ? b.c2 : k == 1 ? b.c1 : k == 2 ? b.c0 : b.cm);
-        if (k == 2) gy = gy + T(0.5) * b.w;
-    }
-    {   // GX[i-1][j]: Y[i][j] is the second half of its face velocity
-        const FluxBar<T> b = tvd_flux_vjp(at(X, i - 1, j - 1), at(X, i - 1, j), at(X, i - 1, j + 1), at(X, i - 1, j + 2),
-                                          half(at(Y, i - 1, j), at(Y, i, j)), s.cfl, cot(LX, i - 1, j, i - 1, j + 1));
-        gy = gy + T(0.5) * b.w;
-    }
+        for (int k = 0; k < 4; ++k) {   // GX[i][q], q = j - 2 + k; Y[i][j] is the first half of the face velocity of GX[i][j]
+            const int q = j - 2 + k;
+            const FluxBar<T> b = tvd_flux_vjp(at(X, i, q - 1), at(X, i, q), at(X, i, q + 1), at(X, i, q + 2),
+                                              half(at(Y, i, q), at(Y, i + 1, q)), s.cfl, cot(LX, i, q, i, q + 1));
+            gx = gx + (k == 0 ? b.c2 : k == 1 ? b.c1 : k == 2 ? b.c0 : b.cm);
+            if (k == 2) gy = gy + T(0.5) * b.w;
+        }
+        {   // GX[i-1][j]: Y[i][j] is the second half of its face velocity
+            const FluxBar<T> b = tvd_flux_vjp(at(X, i - 1, j - 1), at(X, i - 1, j), at(X, i - 1, j + 1), at(X, i - 1, j + 2),
+                                              half(at(Y, i - 1, j), at(Y, i, j)), s.cfl, cot(LX, i - 1, j, i - 1, j + 1));
+            gy = gy + T(0.5) * b.w;
+        }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {   // FY[p][j], p = i - 2 + k; X[i][j] is the first half of the face velocity of FY[i][j]
-        const int p = i - 2 + k;
-        const FluxBar<T> b = tvd_flux_vjp(at(Y, p - 1, j), at(Y, p, j), at(Y, p + 1, j), at(Y, p + 2, j),
-                                          half(at(X, p, j), at(X, p, j + 1)), s.cfl, cot(LY, p, j, p + 1, j));
-        gy = gy + (k == 0 ? b.c2 : k == 1 ? b.c1 : k == 2 ? b.c0 : b.cm);
-        if (k == 2) gx = gx + T(0.5) * b.w;
-    }
-    {   // FY[i][j-1]: X[i][j] is the second half of its face velocity
-        const FluxBar<T> b = tvd_flux_vjp(at(Y, i - 1, j - 1), at(Y, i, j - 1), at(Y, i + 1, j - 1), at(Y, i + 2, j - 1),
-                                          half(at(X, i, j - 1), at(X, i, j)), s.cfl, cot(LY, i, j - 1, i + 1, j - 1));
-        gx = gx + T(0.5) * b.w;
-    }
+        for (int k = 0; k < 4; ++k) {   // FY[p][j], p = i - 2 + k; X[i][j] is the first half of the face velocity of FY[i][j]
+            const int p = i - 2 + k;
+            const FluxBar<T> b = tvd_flux_vjp(at(Y, p - 1, j), at(Y, p, j), at(Y, p + 1, j), at(Y, p + 2, j),
+                                              half(at(X, p, j), at(X, p, j + 1)), s.cfl, cot(LY, p, j, p + 1, j));
+            gy = gy + (k == 0 ? b.c2 : k == 1 ? b.c1 : k == 2 ? b.c0 : b.cm);
+            if (k == 2) gx = gx + T(0.5) * b.w;
+        }
+        {   // FY[i][j-1]: X[i][j] is the second half of its face velocity
+            const FluxBar<T> b = tvd_flux_vjp(at(Y, i - 1, j - 1), at(Y, i, j - 1), at(Y, i + 1, j - 1), at(Y, i + 2, j - 1),
+                                              half(at(X, i, j - 1), at(X, i, j)), s.cfl, cot(LY, i, j - 1, i + 1, j - 1));
+            gx = gx + T(0.5) * b.w;
+        }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {   // GY[i][q], q = j - 2 + k
-        const int q = j - 2 + k;
-        const T c0 = at(Y, i, q), c1 = at(Y, i, q + 1);
-        const FluxBar<T> b = tvd_flux_vjp(at(Y, i, q - 1), c0, c1, at(Y, i, q + 2), half(c0, c1), s.cfl, cot(LY, i, q, i, q + 1));
-        gy = gy + (k == 0 ? b.c2 : k == 1 ? b.c1 + T(0.5) * b.w : k == 2 ? b.c0 + T(0.5) * b.w : b.cm);
+        for (int k = 0; k < 4; ++k) {   // GY[i][q], q = j - 2 + k
+            const int q = j - 2 + k;
+            const T c0 = at(Y, i, q), c1 = at(Y, i, q + 1);
+            const FluxBar<T> b = tvd_flux_vjp(at(Y, i, q - 1), c0, c1, at(Y, i, q + 2), half(c0, c1), s.cfl, cot(LY, i, q, i, q + 1));
+            gy = gy + (k == 0 ? b.c2 : k == 1 ? b.c1 + T(0.5) * b.w : k == 2 ? b.c0 + T(0.5) * b.w : b.cm);
+        }
+    } else {
+        const T x00 = at(X, i, j), y00 = at(Y, i, j);
+        const T xm1 = at(X, i - 1, j), xp1 = at(X, i + 1, j), xjm1 = at(X, i, j - 1), xjp1 = at(X, i, j + 1);
+        const T ym1 = at(Y, i - 1, j), yp1 = at(Y, i + 1, j), yjm1 = at(Y, i, j - 1), yjp1 = at(Y, i, j + 1);
+        {   // FX[i-1][j]: X[i][j] is its c1 and the second half of its face velocity
+            const FaceBar<T> b = face_flux_vjp<SCHEME>(xm1, x00, half(xm1, x00), s.cfl, cot(LX, i - 1, j, i, j));
+            gx = gx + (b.c1 + T(0.5) * b.w);
+        }
+        {   // FX[i][j]: its c0 and the first half of its face velocity
+            const FaceBar<T> b = face_flux_vjp<SCHEME>(x00, xp1, half(x00, xp1), s.cfl, cot(LX, i, j, i + 1, j));
+            gx = gx + (b.c0 + T(0.5) * b.w);
+        }
+        {   // GX[i][j-1]: X[i][j] is its c1
+            const FaceBar<T> b = face_flux_vjp<SCHEME>(xjm1, x00, half(yjm1, at(Y, i + 1, j - 1)), s.cfl, cot(LX, i, j - 1, i, j));
+            gx = gx + b.c1;
+        }
+        {   // GX[i][j]: X[i][j] is its c0, Y[i][j] the first half of its face velocity
+            const FaceBar<T> b = face_flux_vjp<SCHEME>(x00, xjp1, half(y00, yp1), s.cfl, cot(LX, i, j, i, j + 1));
+            gx = gx + b.c0;
+            gy = gy + T(0.5) * b.w;
+        }
+        {   // GX[i-1][j]: Y[i][j] is the second half of its face velocity
+            const FaceBar<T> b = face_flux_vjp<SCHEME>(xm1, at(X, i - 1, j + 1), half(ym1, y00), s.cfl, cot(LX, i - 1, j, i - 1, j + 1));
+            gy = gy + T(0.5) * b.w;
+        }
+        {   // FY[i-1][j]: Y[i][j] is its c1
+            const FaceBar<T> b = face_flux_vjp<SCHEME>(ym1, y00, half(xm1, at(X, i - 1, j + 1)), s.cfl, cot(LY, i - 1, j, i, j));
+            gy = gy + b.c1;
+        }
+        {   // FY[i][j]: Y[i][j] is its c0, X[i][j] the first half of its face velocity
+            const FaceBar<T> b = face_flux_vjp<SCHEME>(y00, yp1, half(x00, xjp1), s.cfl, cot(LY, i, j, i + 1, j));
+            gy = gy + b.c0;
+            gx = gx + T(0.5) * b.w;
+        }
+        {   // FY[i][j-1]: X[i][j] is the second half of its face velocity
+            const FaceBar<T> b = face_flux_vjp<SCHEME>(yjm1, at(Y, i + 1, j - 1), half(xjm1, x00), s.cfl, cot(LY, i, j - 1, i + 1, j - 1));
+            gx = gx + T(0.5) * b.w;
+        }
+        {   // GY[i][j-1]: Y[i][j] is its c1 and the second half of its face velocity
+            const FaceBar<T> b = face_flux_vjp<SCHEME>(yjm1, y00, half(yjm1, y00), s.cfl, cot(LY, i, j - 1, i, j));
+            gy = gy + (b.c1 + T(0.5) * b.w);
+        }
+        {   // GY[i][j]: its c0 and the first half of its face velocity
+            const FaceBar<T> b = face_flux_vjp<SCHEME>(y00, yjp1, half(y00, yjp1), s.cfl, cot(LY, i, j, i, j + 1));
+            gy = gy + (b.c0 + T(0.5) * b.w);
+        }
     }
     // the 5-point Laplacian is symmetric: nu lap(L); drag: -drag L; the forcing does not depend on the state
     const T l00x = at(LX, i, j), l00y = at(LY, i, j);
@@ -360,7 +518,7 @@ __device__ __forceinline__ void explicit_point_vjp(const T* __restrict__ X, cons
 }
 
 // (ox, oy) = J_F(u)^T (lx, ly), or += with accumulate (stage 0 of the reverse step adds straight into the cotangent of u0)
-template <typename T>
+template <int SCHEME, typename T>
 __global__ void __launch_bounds__(256) k_fvm_stage_vjp(const T* __restrict__ ux, const T* __restrict__ uy, const T* __restrict__ lx,
                                                        const T* __restrict__ ly, T* __restrict__ ox, T* __restrict__ oy,
                                                        int accumulate, StageConst<T> s, int n) {
@@ -369,7 +527,7 @@ __global__ void __launch_bounds__(256) k_fvm_stage_vjp(const T* __restrict__ ux,
     if (i >= n || j >= n) return;
     const size_t base = (size_t)blockIdx.z * n * n;
     T gx, gy;
-    explicit_point_vjp(ux + base, uy + base, lx + base, ly + base, i, j, n, s, gx, gy);
+    explicit_point_vjp<SCHEME>(ux + base, uy + base, lx + base, ly + base, i, j, n, s, gx, gy);
     const size_t p = base + (size_t)i * n + j;
     if (accumulate) {
         gx = ox[p] + gx;
@@ -434,6 +592,7 @@ struct tcfd_fvm_plan {
     void* fx;                  // (n, n) forcing / density per component, field precision (NULL: no forcing)
     void* fy;
     size_t fft_ws;             // tcfd_ns2d_workspace_bytes of the transform plan, per batch, computed at call time
+    int scheme;                // TCFD_FVM_*: the instantiation of k_fvm_stage / k_fvm_stage_vjp, read at every launch
 };
 
 // ---- per-precision launchers (one compilation unit each); the C ABI (unit 0) dispatches on the plan's dtype
@@ -468,9 +627,18 @@ int FVMFN(fvm_stage_launch)(const tcfd_fvm_plan* p, const void* ux, const void* 
         tg.c[t] = t < count ? (Real)c[t] : Real(0);
         tg.mode[t] = t < count ? mode[t] : 0;
     }
-    hipLaunchKernelGGL(k_fvm_stage<Real>, cell_grid(p->n, batch), kCellBlock, 0, st, (const Real*)ux, (const Real*)uy,
-                       (const Real*)u0x, (const Real*)u0y, (const Real*)p->fx, (const Real*)p->fy, (Real*)kx, (Real*)ky, tg,
-                       stage_const(p, dt), p->n);
+#define STAGE(SCHEME)                                                                                                      \
+    hipLaunchKernelGGL((k_fvm_stage<SCHEME, Real>), cell_grid(p->n, batch), kCellBlock, 0, st, (const Real*)ux,            \
+                       (const Real*)uy, (const Real*)u0x, (const Real*)u0y, (const Real*)p->fx, (const Real*)p->fy,        \
+                       (Real*)kx, (Real*)ky, tg, stage_const(p, dt), p->n)
+    switch (p->scheme) {
+        case VAN_LEER: STAGE(VAN_LEER); break;
+        case UPWIND: STAGE(UPWIND); break;
+        case LINEAR: STAGE(LINEAR); break;
+        case LAX_WENDROFF: STAGE(LAX_WENDROFF); break;
+        default: return FAIL(TCFD_EINVAL, "fvm: advection scheme %d", p->scheme);
+    }
+#undef STAGE
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -501,8 +669,18 @@ int FVMFN(fvm_apply_launch)(const tcfd_fvm_plan* p, const void* px, const void* 
 
 int FVMFN(fvm_stage_vjp_launch)(const tcfd_fvm_plan* p, const void* ux, const void* uy, const void* lx, const void* ly, void* ox,
                                 void* oy, int accumulate, long batch, double dt, hipStream_t st) {
-    hipLaunchKernelGGL(k_fvm_stage_vjp<Real>, cell_grid(p->n, batch), kCellBlock, 0, st, (const Real*)ux, (const Real*)uy,
-                       (const Real*)lx, (const Real*)ly, (Real*)ox, (Real*)oy, accumulate, stage_const(p, dt), p->n);
+#define STAGE_VJP(SCHEME)                                                                                                  \
+    hipLaunchKernelGGL((k_fvm_stage_vjp<SCHEME, Real>), cell_grid(p->n, batch), kCellBlock, 0, st, (const Real*)ux,        \
+                       (const Real*)uy, (const Real*)lx, (const Real*)ly, (Real*)ox, (Real*)oy, accumulate,                \
+                       stage_const(p, dt), p->n)
+    switch (p->scheme) {
+        case VAN_LEER: STAGE_VJP(VAN_LEER); break;
+        case UPWIND: STAGE_VJP(UPWIND); break;
+        case LINEAR: STAGE_VJP(LINEAR); break;
+        case LAX_WENDROFF: STAGE_VJP(LAX_WENDROFF); break;
+        default: return FAIL(TCFD_EINVAL, "fvm: advection scheme %d", p->scheme);
+    }
+#undef STAGE_VJP
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -656,6 +834,7 @@ int tcfd_fvm_plan_create(tcfd_fvm_plan** out, int n, int dtype, double h, double
     p->nu = nu_over_density;
     p->drag = drag;
     p->fft = fft;
+    p->scheme = TCFD_FVM_VAN_LEER;
     const bool f64 = dtype == TCFD_C128;
     auto upload = [&](const double* src, size_t count, void** dst) -> int {
         const size_t bytes = count * (f64 ? 8 : 4);
@@ -688,6 +867,15 @@ void tcfd_fvm_plan_destroy(tcfd_fvm_plan* p) {
     if (p->fy) (void)hipFree(p->fy);
     if (p->fft) tcfd_ns2d_plan_destroy(p->fft);
     delete p;
+}
+
+int tcfd_fvm_plan_set_advection(tcfd_fvm_plan* p, int scheme) {
+    if (scheme != TCFD_FVM_VAN_LEER && scheme != TCFD_FVM_UPWIND && scheme != TCFD_FVM_LINEAR && scheme != TCFD_FVM_LAX_WENDROFF)
+        return FAIL(TCFD_EINVAL, "fvm_plan_set_advection: unknown advection scheme %d (TCFD_FVM_VAN_LEER = 0, TCFD_FVM_UPWIND = 1, "
+                                 "TCFD_FVM_LINEAR = 2, TCFD_FVM_LAX_WENDROFF = 3)", scheme);
+    if (!p) return FAIL(TCFD_EINVAL, "fvm_plan_set_advection: null plan");
+    p->scheme = scheme;
+    return 0;
 }
 
 size_t tcfd_fvm_workspace_bytes(const tcfd_fvm_plan* p, long batch) {

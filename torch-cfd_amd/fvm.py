@@ -13,12 +13,17 @@ project's own rfft2 / irfft2 kernels.  Gradients with respect to the velocity fl
 ``get_trajectory_fvm`` when grad mode is on and ``ux`` or ``uy`` requires grad: ``fvm_autograd.py`` runs the HIP adjoint
 kernels.  A stepping call under grad keeps the input of each of its K steps, ``K * 2 * B * n^2 * w`` bytes (``w`` = 8 for
 fp64, 4 for fp32), until its backward has run.  A tableau whose parameters require grad raises while grad mode is on.
+
+The advection scheme is the equation's ``convect`` argument: ``convect`` (van Leer, the default) or
+``advection(interpolation.upwind | linear | lax_wendroff)``, the counterparts of the reference's ``convect`` and of an
+``advect_general`` with that ``c_interpolation_fn``.  Each is one instantiation of the stage kernel and of its adjoint.
 """
 from __future__ import annotations
 
 import ctypes
 import math
 import weakref
+from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -26,6 +31,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import fvm_autograd as _ad
+from . import interpolation
 from .grids import Grid
 
 _FP = {torch.float64: _lib.TCFD_C128, torch.float32: _lib.TCFD_C64}
@@ -64,6 +70,56 @@ def _square_step(grid: Grid) -> float:
     if grid.ndim != 2 or grid.shape[0] != grid.shape[1] or not math.isclose(grid.step[0], grid.step[1], rel_tol=0, abs_tol=0):
         raise NotImplementedError(f"{grid}: the finite-volume solver runs on square n x n grids with equal cell sizes")
     return grid.step[0]
+
+
+# ----------------------------------------------------------------------------- advection scheme
+@dataclass(frozen=True)
+class Convect:
+    """The advection term of the equation as a descriptor (compares and hashes by value): how the transported component
+    (``c_interpolation_fn``) and the velocity (``u_interpolation_fn``) reach the faces of the control volume.  The counterpart
+    of a ``convect`` function built from the reference's ``advect_general``; build one with ``advection``."""
+
+    c_interpolation_fn: interpolation.Interpolation
+    u_interpolation_fn: interpolation.Interpolation = interpolation.linear
+
+    @property
+    def scheme(self) -> int:
+        """The ``TCFD_FVM_*`` value of the kernel instantiation."""
+        return self.c_interpolation_fn.scheme
+
+    def __repr__(self) -> str:
+        return f"fvm.advection({self.c_interpolation_fn!r})"
+
+
+def advection(c_interpolation_fn, u_interpolation_fn=interpolation.linear) -> Convect:
+    """``convect`` argument of ``NavierStokes2DFVMProjection`` for advection by
+    ``advect_general(c, v, u_interpolation_fn, c_interpolation_fn, dt)`` of every velocity component (torch_cfd/fvm.py:89).
+    ``c_interpolation_fn``: ``interpolation.upwind``, ``linear``, ``lax_wendroff`` or
+    ``apply_tvd_limiter(lax_wendroff, van_leer_limiter)``; the face velocity is interpolated linearly, as everywhere in the
+    reference."""
+    if not isinstance(c_interpolation_fn, interpolation.Interpolation):
+        raise TypeError(f"advection: c_interpolation_fn = {c_interpolation_fn!r} is not a scheme of torch_cfd_amd.interpolation "
+                        f"({_SCHEMES_TEXT}); arbitrary Python interpolation cannot run in the HIP kernels")
+    if u_interpolation_fn != interpolation.linear:
+        raise NotImplementedError(f"advection: u_interpolation_fn = {u_interpolation_fn!r}: the kernels interpolate the face "
+                                  "velocity with interpolation.linear only")
+    return Convect(c_interpolation_fn, interpolation.linear)
+
+
+_SCHEMES_TEXT = ("interpolation.upwind, interpolation.linear, interpolation.lax_wendroff, "
+                 "interpolation.apply_tvd_limiter(interpolation.lax_wendroff, interpolation.van_leer_limiter)")
+
+# van Leer: the counterpart of the reference's module-level ``convect`` (advect_van_leer_using_limiters of every component)
+convect = _VAN_LEER_CONVECT = advection(interpolation.apply_tvd_limiter(interpolation.lax_wendroff, interpolation.van_leer_limiter))
+
+
+def _as_convect(c) -> Convect:
+    if c is None:
+        return _VAN_LEER_CONVECT
+    if isinstance(c, Convect):
+        return c
+    raise TypeError(f"convect = {c!r}: arbitrary Python advection cannot run in the HIP kernels of the finite-volume solver. "
+                    f"Pass fvm.convect (van Leer, the default) or fvm.advection(c) with c one of {_SCHEMES_TEXT}.")
 
 
 # ----------------------------------------------------------------------------- tableau
@@ -163,7 +219,8 @@ class _FvmPlan:
     """Owns one ``tcfd_fvm_plan`` (inverse-eigenvalue and forcing tables) + a workspace."""
 
     def __init__(self, n: int, dtype: torch.dtype, device: torch.device, h: float, nu: float, drag: float,
-                 inverse: torch.Tensor, force: Optional[Tuple[torch.Tensor, torch.Tensor]]):
+                 inverse: torch.Tensor, force: Optional[Tuple[torch.Tensor, torch.Tensor]],
+                 scheme: int = _lib.TCFD_FVM_VAN_LEER):
         self.lib = _lib.load()
         self.n, self.dtype, self.device = n, dtype, torch.device(device)
         if self.device.type != "cuda":
@@ -184,6 +241,8 @@ class _FvmPlan:
         self.handle = handle
         self._ws: Optional[torch.Tensor] = None
         self._finalizer = weakref.finalize(self, self.lib.tcfd_fvm_plan_destroy, handle)
+        self.scheme = int(scheme)   # fixed for the plan's life: a pending backward holds the plan and so its scheme
+        _lib.check(self.lib.tcfd_fvm_plan_set_advection(handle, self.scheme), "tcfd_fvm_plan_set_advection")
 
     def workspace(self, batch: int, need: Optional[int] = None) -> torch.Tensor:
         """At least ``need`` bytes (default: what ``tcfd_fvm_step`` needs for ``batch``)."""
@@ -367,16 +426,19 @@ class PressureProjection(nn.Module):
 # ----------------------------------------------------------------------------- the equation
 class NavierStokes2DFVMProjection(nn.Module):
     """Incompressible Navier-Stokes on the MAC grid: explicit RK stages of
-    ``du/dt = -(u . grad) u (van Leer) + nu / density lap u + forcing / density - drag u``, each stage state and the result
-    projected onto discretely divergence-free fields (torch_cfd/fvm.py:334).
+    ``du/dt = -(u . grad) u + nu / density lap u + forcing / density - drag u``, each stage state and the result
+    projected onto discretely divergence-free fields (torch_cfd/fvm.py:334).  ``convect`` is the advection scheme:
+    ``fvm.convect`` (van Leer; also ``None``) or ``fvm.advection(interpolation.upwind | linear | lax_wendroff)``; any other
+    callable raises ``TypeError``, since Python advection cannot run in the kernels.
 
     ``forward(u, dt, steps=1)`` runs ``steps`` steps of ``solver`` (an ``RKStepper``) in one device call and returns the
-    pair ``(ux, uy)``; ``explicit_terms(u, dt)`` and ``pressure_projection(u)`` are the two halves on their own.  All three
+    pair ``(ux, uy)``; ``explicit_terms(u, dt)`` and ``pressure_projection(u)`` are the two halves on their own, and
+    ``convect(u, dt)`` is the advection term alone.  All four
     are differentiable with respect to ``u`` (``fvm_autograd.py``); under grad, ``forward`` runs one device call per step
     and keeps each step's input, ``steps * 2 * B * n^2 * w`` bytes, for its backward."""
 
     def __init__(self, viscosity: float, grid: Grid, bcs=None, drag: float = 0.0, density: float = 1.0, forcing=None,
-                 solver: Optional[RKStepper] = None, **kwargs):
+                 solver: Optional[RKStepper] = None, convect: Optional[Convect] = _VAN_LEER_CONVECT, **kwargs):
         super().__init__()
         _check_periodic(bcs)
         _square_step(grid)
@@ -387,8 +449,10 @@ class NavierStokes2DFVMProjection(nn.Module):
         self.drag = drag
         self.forcing = forcing
         self.solver = solver
+        self.advection = _as_convect(convect)
         self._projection = PressureProjection(grid=grid)
         self._plans: Dict[tuple, _FvmPlan] = {}
+        self._convect_plans: Dict[tuple, _FvmPlan] = {}
 
     def _force_tables(self):
         """(fx, fy) / density at the staggered offsets, sampled once per plan (the forcing is state independent)."""
@@ -397,18 +461,45 @@ class NavierStokes2DFVMProjection(nn.Module):
         f = self.forcing(self.grid, None)
         return tuple(_tensor_of(c).detach().to("cpu", torch.float64) / self.density for c in f)
 
-    def _plan(self, dtype, device) -> _FvmPlan:
+    def _plan_key(self, dtype, device) -> tuple:
         inv = self._projection.solver.inverse
         fkey = None if self.forcing is None else getattr(self.forcing, "fingerprint", lambda: id(self.forcing))()
-        key = (torch.device(device), dtype, self.grid.shape[0], float(self.viscosity), float(self.density), float(self.drag),
-               fkey, id(inv), inv._version)
+        return (torch.device(device), dtype, self.grid.shape[0], float(self.viscosity), float(self.density), float(self.drag),
+                fkey, id(inv), inv._version, self.advection.scheme)
+
+    def _plan(self, dtype, device) -> _FvmPlan:
+        key = self._plan_key(dtype, device)
         plan = self._plans.get(key)
         if plan is None:
             self._plans.clear()
             plan = _FvmPlan(self.grid.shape[0], dtype, device, _square_step(self.grid), self.viscosity / self.density,
-                            self.drag, inv, self._force_tables())
+                            self.drag, self._projection.solver.inverse, self._force_tables(), self.advection.scheme)
             self._plans[key] = plan
         return plan
+
+    def _convect_plan(self, dtype, device) -> _FvmPlan:
+        """The plan of the advection term alone: no viscosity, no drag, no forcing.  A second full plan, created at the first
+        ``convect`` call: it uploads the inverse-eigenvalue table again and owns a transform plan it never runs, and a
+        differentiable call holds it until its backward (the autograd node keeps the reference, so clearing the cache
+        below is safe)."""
+        inv = self._projection.solver.inverse
+        key = (torch.device(device), dtype, self.grid.shape[0], id(inv), inv._version, self.advection.scheme)
+        plan = self._convect_plans.get(key)
+        if plan is None:
+            self._convect_plans.clear()
+            plan = _FvmPlan(self.grid.shape[0], dtype, device, _square_step(self.grid), 0.0, 0.0, inv, None,
+                            self.advection.scheme)
+            self._convect_plans[key] = plan
+        return plan
+
+    def convect(self, u, dt: float):
+        """The advection term ``-(u . grad) u`` of the equation's scheme as a pair ``(ux, uy)`` (the reference's
+        ``self.convect(v, dt)``): the explicit-terms kernel on a plan without viscosity, drag and forcing."""
+        ux, uy = _as_pair(u)
+        plan = self._convect_plan(ux.dtype, ux.device)
+        if _ad.wants_grad(ux, uy):
+            return _ad.ExplicitTermsFn.apply(plan, dt, ux, uy)
+        return plan.explicit_terms(ux, uy, dt)
 
     def explicit_terms(self, u, dt: float):
         ux, uy = _as_pair(u)
