@@ -69,7 +69,9 @@ const char* tcfd_last_error(void);
  * tcfd_ns2d_refine_vjp, tcfd_ns2d_refine_workspace_bytes; 11: tcfd_grf_spectrum, tcfd_grf_spectrum_workspace_bytes;
  * 12: tcfd_residual_loss, tcfd_residual_loss_backward, tcfd_residual_loss_supported, tcfd_residual_workspace_bytes, tcfd_lp_sums,
  * tcfd_lp_sums_bwd, tcfd_lp_sums_workspace_bytes, tcfd_h1_sums, tcfd_h1_sums_bwd, tcfd_h1_sums_workspace_bytes;
- * 13: tcfd_fvm_plan_set_advection and the TCFD_FVM_* advection schemes; no earlier entry point changed).  A host compares it with the TCFD_ABI_VERSION it was written against BEFORE the
+ * 13: tcfd_fvm_plan_set_advection and the TCFD_FVM_* advection schemes; no earlier entry point changed).
+ * The tcfd_data_* entry points were ADDED under revision 13 without a new number (no argument list or meaning of an existing
+ * entry changed); a host that needs them looks the symbols up, as torch-cfd_amd/datasets.py does.  A host compares it with the TCFD_ABI_VERSION it was written against BEFORE the
  * first call: a stale prebuilt library would otherwise be called with the wrong argument layout and return garbage
  * (torch-cfd_amd/_lib.py::load does). */
 int tcfd_version(void);
@@ -621,6 +623,40 @@ int tcfd_fvm_step_vjp(const tcfd_fvm_plan* plan, const void* saved, const void* 
 size_t tcfd_grf_spectrum_workspace_bytes(long batch, int n, int normalize);
 int tcfd_grf_spectrum(const void* noise, const void* sqrt_eig, void* out, long batch, int n0, int n, int dtype, int normalize,
                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- training data path: batches from device-resident fields, Gaussian normalisers (added under revision 13) -------------------
+ * Replaces the per-sample CPU work of fno/datasets.py (SpatioTemporalDataset.__getitem__ :431-453,
+ * SpatioTemporalDatasetFixedTime.__getitem__ :554-564, the collate step and the .to(device) of the loader) and the
+ * statistics / transforms of UnitGaussianNormalizer and SpatialGaussianNormalizer (:21-121).  Real data only: a dtype is
+ * TCFD_C64 for float, TCFD_C128 for double.  idx / starts are DEVICE arrays of int64; an entry outside the source writes
+ * nothing for its sample (the caller validates the lists on the host).  No workspace.
+ *
+ * window: for k < count, row = idx[k], s = starts[k]:
+ *     out_in [k][p][t] = src(row, s + t, p),          t < steps
+ *     out_out[k][p][t] = src(row, s + steps + t, p),  t < out_steps,    p < points
+ *   src is (rows, total_steps, points) or, with time_last != 0, (rows, points, total_steps); the outputs are cast to
+ *   dst_dtype.  steps, out_steps <= 64; count <= 65535.
+ * fno3d_batch: out_input (count, 3 + steps, n, n, out_steps): channels 0, 1, 2 = grid_x[i], grid_y[j], grid_t[t] (host-filled
+ *   tables of the OUTPUT dtype with n, n, out_steps entries), channel 3 + c = field(idx[k], c, i, j) for every t;
+ *   out_target[k] = target(idx[k]).  field is (rows, steps, n, n), target (rows, n, n, out_steps), both src_dtype.
+ *   count * (4 + steps) <= 65535.
+ * affine: element e of x uses statistic i = (e / inner) % stat_count;
+ *     mode 0: out = (x - mean[i]) / (std[i] + eps)       mode 1: out = x * (std[i] + eps) + mean[i]
+ *   std + eps is rounded in stat_dtype, everything else in the wider of x_dtype and stat_dtype (true division, the product
+ *   rounded before the sum), then cast to out_dtype.  mean == NULL stands for zeros: that is the derivative of either mode
+ *   applied to a cotangent.  out may alias x when the two dtypes agree.
+ * moments: x (rows, stat_count, inner) contiguous; mean and unbiased std over the rows and the inner axis (inner = 1: over
+ *   axis 0 alone).  Two passes accumulated in double in a fixed order, no atomics: two runs give the same bits. */
+int tcfd_data_window(const void* src, void* out_in, void* out_out, const void* idx, const void* starts, long count, long rows,
+                     long total_steps, long points, int steps, int out_steps, int time_last, int src_dtype, int dst_dtype,
+                     void* stream);
+int tcfd_data_fno3d_batch(const void* field, const void* target, const void* idx, const void* grid_x, const void* grid_y,
+                          const void* grid_t, void* out_input, void* out_target, long count, long rows, int steps, int n,
+                          int out_steps, int src_dtype, int dst_dtype, void* stream);
+int tcfd_data_affine(const void* x, const void* mean, const void* std_, void* out, long total, long stat_count, long inner,
+                     double eps, int mode, int x_dtype, int stat_dtype, int out_dtype, void* stream);
+int tcfd_data_moments(const void* x, void* mean, void* std_, long rows, long stat_count, long inner, int x_dtype, int stat_dtype,
+                      void* stream);
 
 #endif /* TCFD_H_TYPES_ONLY */
 

@@ -20,6 +20,8 @@ from .equations import (  # noqa: F401
 from .forcings import FieldArray, ForcingFn, KolmogorovForcing, SimpleSolenoidalForcing, SinCosForcing  # noqa: F401
 from .solvers import get_trajectory_imex  # noqa: F401
 from .grf import GRF2d  # noqa: F401
+from . import datasets, pipeline  # noqa: F401  (device-resident data sets, normalisers, BatchLoader; the batch loops)
+from .datasets import BatchLoader, SpatioTemporalDataset, SpatioTemporalDatasetFixedTime  # noqa: F401
 from .fvm import NavierStokes2DFVMProjection, PressureProjection, RKStepper, get_trajectory_fvm  # noqa: F401
 from . import fvm, interpolation  # noqa: F401  (fvm.advection / fvm.convect and the scheme descriptors)
 from .fvm import advection  # noqa: F401

@@ -25,7 +25,7 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_NAME = "libtcfd_hip.so"
 LIB_PATH = os.path.join(CSRC, LIB_NAME)
 SOURCES = ("tcfd_ns2d.hip", "tcfd_fno.hip", "tcfd_fno_pw.hip", "tcfd_fno_tiles.hip", "tcfd_fno3d.hip", "tcfd_loss.hip", "tcfd_fvm.hip",
-           "tcfd_grf.hip", "tcfd_residual.hip")
+           "tcfd_grf.hip", "tcfd_residual.hip", "tcfd_data.hip")
 
 TCFD_C64, TCFD_C128 = 0, 1
 # advection schemes of a finite-volume plan (include/tcfd.h TCFD_FVM_*)
@@ -89,7 +89,8 @@ JOBS = (("tcfd_ns2d.hip", ("-DTCFD_UNIT=0",), "tcfd_ns2d.o"),
         ("tcfd_grf.hip", (), "tcfd_grf.o"),
         # the residual loss, twice as well: unit 0 = C ABI + float64 kernels + the small losses, unit 1 = float32 kernels
         ("tcfd_residual.hip", ("-DTCFD_RES_UNIT=0",), "tcfd_residual.o"),
-        ("tcfd_residual.hip", ("-DTCFD_RES_UNIT=1",), "tcfd_residual_f32.o"))
+        ("tcfd_residual.hip", ("-DTCFD_RES_UNIT=1",), "tcfd_residual_f32.o"),
+        ("tcfd_data.hip", (), "tcfd_data.o"))
 
 
 def _build_locked(srcs, verbose):
@@ -224,6 +225,10 @@ SIGNATURES = {
     "tcfd_h1_sums_workspace_bytes": (_sz, [_l, _i, _i, _i]),
     "tcfd_h1_sums": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _l, _i, _i, _i, _d, _i, _vp, _sz, _vp]),
     "tcfd_h1_sums_bwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _l, _i, _i, _i, _d, _i, _vp]),
+    "tcfd_data_window": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _i, _i, _i, _i, _i, _vp]),
+    "tcfd_data_fno3d_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _i, _i, _i, _i, _i, _vp]),
+    "tcfd_data_affine": (_i, [_vp, _vp, _vp, _vp, _l, _l, _l, _d, _i, _i, _i, _i, _vp]),
+    "tcfd_data_moments": (_i, [_vp, _vp, _vp, _l, _l, _l, _i, _i, _vp]),
 }
 
 
