@@ -70,8 +70,9 @@ const char* tcfd_last_error(void);
  * 12: tcfd_residual_loss, tcfd_residual_loss_backward, tcfd_residual_loss_supported, tcfd_residual_workspace_bytes, tcfd_lp_sums,
  * tcfd_lp_sums_bwd, tcfd_lp_sums_workspace_bytes, tcfd_h1_sums, tcfd_h1_sums_bwd, tcfd_h1_sums_workspace_bytes;
  * 13: tcfd_fvm_plan_set_advection and the TCFD_FVM_* advection schemes; no earlier entry point changed).
- * The tcfd_data_* entry points were ADDED under revision 13 without a new number (no argument list or meaning of an existing
- * entry changed); a host that needs them looks the symbols up, as torch-cfd_amd/datasets.py does.  A host compares it with the TCFD_ABI_VERSION it was written against BEFORE the
+ * The tcfd_data_* entry points and the tangent-linear ones (tcfd_ns2d_explicit_terms_jvp, tcfd_ns2d_step_jvp,
+ * tcfd_ns2d_jvp_workspace_bytes) were ADDED under revision 13 without a new number (no argument list or meaning of an existing
+ * entry changed); a host that needs them looks the symbols up, as torch-cfd_amd/datasets.py and _HipPlan.jvp_workspace do.  A host compares it with the TCFD_ABI_VERSION it was written against BEFORE the
  * first call: a stale prebuilt library would otherwise be called with the wrong argument layout and return garbage
  * (torch-cfd_amd/_lib.py::load does). */
 int tcfd_version(void);
@@ -157,6 +158,31 @@ int tcfd_ns2d_explicit_terms(const tcfd_ns2d_plan* plan, const void* w, void* ou
  * (lap = -4 pi^2 |k|^2 with lap(0,0) := 1).  Workspace as tcfd_ns2d_explicit_terms. */
 int tcfd_ns2d_explicit_terms_vjp(const tcfd_ns2d_plan* plan, const void* w, const void* gm, void* xout, long batch,
                                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- tangent-linear model (forward-mode Jacobian-vector product) --------------
+ * What torch.autograd.forward_ad derives from the ~40 ops of NavierStokes2DSpectral._explicit_terms and from the stepper when
+ * the state carries a tangent.  With F(w) = mask . rfft2(-(dxw u + dyw v)) + f and a perturbation dw of w,
+ *     F'(w) dw = mask . rfft2(-(ddxw u + dxw du + ddyw v + dyw dv)),   d-fields = irfft2(a_f dw)   (no forcing term)
+ * is computed in the same sweep as F(w): the opening column pass runs on w and on dw, ONE row pass carries both through the
+ * advection (eight c2r, two r2c per row pair), the closing column pass runs on both products.
+ *   w, dw           (batch, n, m) complex, read only
+ *   out_f           (batch, n, m) complex or NULL: F(w)           out_df   (batch, n, m) complex: F'(w) dw
+ * tcfd_ns2d_step_jvp: `steps` steps of the schedule of tcfd_ns2d_step_imex (same fa / beta / gdt / mu_num / mu_den / base0,
+ * the same three may be NULL) on the pair: every stage is the sweep above followed by the stage update on the state and, with
+ * the same coefficients, on the tangent (the update is linear; the tangent's accumulator starts from 0 every step like the
+ * state's).  w_out / dw_out: the state and the tangent after the last step; they may alias w_in / dw_in respectively.
+ * Workspace of both: tcfd_ns2d_jvp_workspace_bytes(plan, batch) -- 16 chunk-sized fields (two plane sets, two advection
+ * fields, h and dh, two intermediate states each); the calls run chunk by chunk, a chunk holding half the batch elements of a
+ * chunk of tcfd_ns2d_step, so it stops growing at one chunk -- except where tcfd_ns2d_step itself runs the whole batch at once
+ * (fewer than three fields per cache-sized chunk and n < 2048: n = 1280, 1536 in complex128), where it is 16 fields of the
+ * whole batch.  No atomics: two runs give the same bits. */
+size_t tcfd_ns2d_jvp_workspace_bytes(const tcfd_ns2d_plan* plan, long batch);
+int tcfd_ns2d_explicit_terms_jvp(const tcfd_ns2d_plan* plan, const void* w, const void* dw, void* out_f, void* out_df,
+                                 long batch, void* workspace, size_t workspace_bytes, void* stream);
+int tcfd_ns2d_step_jvp(const tcfd_ns2d_plan* plan, const void* w_in, const void* dw_in, void* w_out, void* dw_out, long batch,
+                       int nstages, const double* fa, const double* beta, const double* gdt, const double* mu_num,
+                       const double* mu_den, const int* base0, int steps, void* workspace, size_t workspace_bytes,
+                       void* stream);
 
 /* wbar (batch, plane) = sum_f post_f (.) X_f: the closing sum of the vector-Jacobian product above (X = xout, post (4, plane)
  * complex tables -(c / n^2) conj(a_f) built by the caller) in one pass. */

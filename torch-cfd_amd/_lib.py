@@ -135,6 +135,10 @@ SIGNATURES = {
                                  _vp]),
     "tcfd_ns2d_explicit_terms": (_i, [_vp, _vp, _vp, _l, _vp, _sz, _vp]),
     "tcfd_ns2d_explicit_terms_vjp": (_i, [_vp, _vp, _vp, _vp, _l, _vp, _sz, _vp]),
+    "tcfd_ns2d_jvp_workspace_bytes": (_sz, [_vp, _l]),
+    "tcfd_ns2d_explicit_terms_jvp": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _vp, _sz, _vp]),
+    "tcfd_ns2d_step_jvp": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _i, _dp, _dp, _dp, _dp, _dp, ctypes.POINTER(_i), _i, _vp, _sz,
+                                _vp]),
     "tcfd_ns2d_vjp_combine": (_i, [_vp, _vp, _vp, _l, _l, _i, _vp]),
     "tcfd_ns2d_stage_update": (_i, [_vp, _vp, _vp, _vp, ctypes.POINTER(_d), _vp, _vp, _l, _l, _i, _vp]),
     "tcfd_ns2d_stage_update_vjp": (_i, [_vp, _vp, _vp, ctypes.POINTER(_d), _vp, _vp, _vp, _l, _l, _i, _vp]),

@@ -831,6 +831,93 @@ __global__ __launch_bounds__((RowGeom<T, N, EPT, THR>::THREADS)) void k_rows_vjp
     }
 }
 
+// ---- row pass of the JACOBIAN-VECTOR PRODUCT (tangent-linear model) of the explicit terms ---------------------------------
+// A state w and a perturbation dw ride through the advection together:  with the four planes of w (`planes`) and of dw
+// (`dplanes`, same layout),
+//     p  = -(u dxw + v dyw)                                   -> adv   (the advection of the state, as k_rows_advect5 writes it)
+//     dp = -(ddxw u + dxw du + ddyw v + dyw dv)               -> dadv  (its directional derivative along dw)
+// One group per row pair, two rows per complex transform as in v5 / k_rows_vjp: eight c2r, two r2c.  Plane order
+//     u, ddxw, dxw, du | v, ddyw, dyw, dv
+// Each perturbation transform is folded into dp as soon as its state partner is there, and u (v) is dead once p has taken
+// u dxw (v dyw): besides p and dp ONE kept transform (`k`) and the working one (`w`) are live -- four arrays of EPT elements, as
+// in k_rows_vjp.  The eight inverse transforms are ONE piece of code in a loop that is not unrolled (the plane and what its
+// transform is folded into are selected by the loop index): unrolled, the whole row pair is a single scheduling region in
+// which the compiler keeps the loads, twiddles and addresses of several transforms in flight, and every instantiation with
+// EPT >= 12 spilled in fp64.  Plain (non-split) plane layout, rows read right before use (no prefetch registers).
+// PART = 0: both outputs in one sweep; 1: p only, 2: dp only (re-reading the state planes) -- the two-pass form for the sizes
+// whose one-pass form would not fit the register file.
+template <typename T, int N, int EPT, int THR, int PART>
+__global__ __launch_bounds__((RowGeom<T, N, EPT, THR>::THREADS)) void k_rows_jvp(const cx<T>* __restrict__ planes,
+                                                                                 const cx<T>* __restrict__ dplanes,
+                                                                                 size_t plane_stride, cx<T>* __restrict__ adv,
+                                                                                 cx<T>* __restrict__ dadv,
+                                                                                 const cx<T>* __restrict__ tw, long npairs, int ld) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    using Gm = RowGeom<T, N, EPT, THR>;
+    constexpr int G = Gm::G;
+    constexpr bool WG = (G > 64);
+    constexpr bool DO_P = (PART != 2), DO_D = (PART != 1);
+    const int grp = threadIdx.x / G;
+    const int j = threadIdx.x % G;
+    cx<T>* lds = reinterpret_cast<cx<T>*>(smem_raw) + (size_t)grp * Gm::LDS_PER_GROUP;
+    const long stride = (long)gridDim.x * Gm::GROUPS;
+    long pair = (long)blockIdx.x * Gm::GROUPS + grp;
+    const long iters = (npairs + stride - 1) / stride;   // every group runs the same number of iterations (workgroup barriers)
+    for (long it = 0; it < iters; ++it, pair += stride) {
+        const bool valid = pair < npairs;
+        const long cur = valid ? pair : npairs - 1;
+        const size_t off = (size_t)cur * 2 * (size_t)ld;
+        cx<T> k[EPT], w[EPT];
+        [[maybe_unused]] cx<T> p[EPT], dp[EPT];
+#pragma unroll
+        for (int t = 0; t < EPT; ++t) {
+            if constexpr (DO_P) p[t] = mk<T>((T)0, (T)0);
+            if constexpr (DO_D) dp[t] = mk<T>((T)0, (T)0);
+        }
+        // s = 4 c + r: velocity component c (0: u with dx w, 1: v with dy w), role r of the transform
+        //   r = 0: k <- u        r = 1: dp += d(dxw) k        r = 2: p += k dxw, k <- dxw        r = 3: dp += k du
+#pragma unroll 1
+        for (int s = 0; s < 8; s += (DO_D ? 1 : 2)) {   // (p alone: the state's planes only)
+            const int c = s >> 2, r = s & 3;
+            const int f = (r == 0 || r == 3) ? c : 2 + c;
+            const cx<T>* rowA = ((r & 1) ? dplanes : planes) + (size_t)f * plane_stride + off;
+            {
+                RawPair<T, EPT> H;
+                load_raw<T, N, EPT>(H, rowA, rowA + ld, j);
+                pack_herm<T, N, EPT, WG>(w, H, lds, j);
+            }
+            tile_fft<T, N, EPT, +1, 1, true, WG>(w, lds, tw, j, 0);
+            if (r == 0) {
+#pragma unroll
+                for (int t = 0; t < EPT; ++t) k[t] = w[t];
+            } else if (r == 2) {
+#pragma unroll
+                for (int t = 0; t < EPT; ++t) {
+                    if constexpr (DO_P) p[t] = mk<T>(p[t].x + k[t].x * w[t].x, p[t].y + k[t].y * w[t].y);
+                    if constexpr (DO_D) k[t] = w[t];
+                }
+            } else {
+                if constexpr (DO_D) {
+#pragma unroll
+                    for (int t = 0; t < EPT; ++t) dp[t] = mk<T>(dp[t].x + w[t].x * k[t].x, dp[t].y + w[t].y * k[t].y);
+                }
+            }
+        }
+        if constexpr (DO_P) {
+#pragma unroll
+            for (int t = 0; t < EPT; ++t) p[t] = mk<T>(-p[t].x, -p[t].y);
+            tile_fft<T, N, EPT, -1, 1, true, WG>(p, lds, tw, j, 0);
+            unpack_store_pair<T, N, EPT>(p, lds, adv + off, adv + off + ld, j, valid);
+        }
+        if constexpr (DO_D) {
+#pragma unroll
+            for (int t = 0; t < EPT; ++t) dp[t] = mk<T>(-dp[t].x, -dp[t].y);
+            tile_fft<T, N, EPT, -1, 1, true, WG>(dp, lds, tw, j, 0);
+            unpack_store_pair<T, N, EPT>(dp, lds, dadv + off, dadv + off + ld, j, valid);
+        }
+    }
+}
+
 // ---- row pass, one plane per transform ("v5") --------------------------------------------------
 // Round 1 rode two PLANES of one row through a complex transform, so the transformed velocity rows of BOTH rows of a pair
 // stayed live while the gradient planes were transformed (256 VGPR + 84 AGPR, one wave per SIMD at 1024^2 fp64; kernels v3 / v4,
@@ -1593,7 +1680,7 @@ static int line_group(const tcfd_ns2d_plan* p) {
 }
 
 template <typename T, int N, int MODE, int EPT, int C, int MINW = 1, int SP = 0>
-static int launch_cols_v(const tcfd_ns2d_plan* p, ColArgs<T> a, long batch, hipStream_t st) {
+static int launch_cols_v(const tcfd_ns2d_plan* p, ColArgs<T> a, long batch, hipStream_t st, bool no_forcing = false) {
     constexpr int NT = N >> SP;
     constexpr int G = NT / EPT;
     // + TCFD_COLS_LDS_PAD bytes: an experiment knob that caps the workgroups a CU takes (occupancy A/B without a rebuild)
@@ -1617,6 +1704,11 @@ static int launch_cols_v(const tcfd_ns2d_plan* p, ColArgs<T> a, long batch, hipS
     a.f_nnz = (p->f_sparse && p->f_nnz <= 32) ? p->f_nnz : 0;
     a.f_row = (const int*)p->f_row;
     a.f_val = (const cx<T>*)p->f_val;
+    if (no_forcing) {   // the tangent of F carries no forcing term: this launch's copy of the arguments points at none
+        a.forcing = nullptr;
+        a.f_ptr = nullptr;
+        a.f_nnz = 0;
+    }
     a.sep = p->sep;
     a.keep_cols = p->keep_cols;
     a.tw = (const cx<T>*)(SP ? p->tw2 : p->tw);
@@ -2424,6 +2516,236 @@ TCFD_API int tcfd_ns2d_explicit_terms_vjp(const tcfd_ns2d_plan* p, const void* w
         const long nb = std::min(chunk, batch - b0);
         rc = explicit_vjp_dispatch(p, (const unsigned char*)w + (size_t)b0 * esz, (const unsigned char*)gm + (size_t)b0 * esz,
                                    (unsigned char*)xout + (size_t)b0 * esz, xs, nb, ws, st);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------ tangent-linear model (forward-mode JVP)
+// F'(w) dw = M . R( -(ddxw u + dxw du + ddyw v + dyw dv) ),  d-fields = I(a_f dw): no forcing term.  Per chunk: the opening
+// column pass twice (w and dw -> two sets of four planes, plain layout, whole-column tiles as explicit_vjp_impl), ONE row pass
+// (k_rows_jvp) that carries both through the advection, the closing column pass for p (mask + forcing) and for dp (mask only).
+// Scratch: 16 chunk-sized fields -- two plane sets, two advection fields, h and dh, and the two intermediate states of the
+// stepper for w and dw.  F and dF of a stage land in plane 0 of their sets (the planes are dead after the row pass).
+template <typename T>
+struct JvpWs {
+    cx<T>* planes;
+    cx<T>* dplanes;
+    cx<T>* adv;
+    cx<T>* dadv;
+    cx<T>* h;
+    cx<T>* dh;
+    cx<T>* s[2];          // intermediate states (caller layout, pitch m)
+    cx<T>* ds[2];
+    size_t plane_stride;  // elements
+};
+template <typename T>
+static JvpWs<T> carve_jvp(const tcfd_ns2d_plan* p, void* ws, long batch) {
+    const size_t fb = field_bytes(p, batch);
+    unsigned char* base = (unsigned char*)ws;
+    auto at = [&](int i) { return (cx<T>*)(base + (size_t)i * fb); };
+    JvpWs<T> w;
+    w.planes = at(0);
+    w.dplanes = at(4);
+    w.adv = at(8);
+    w.dadv = at(9);
+    w.h = at(10);
+    w.dh = at(11);
+    w.s[0] = at(12);
+    w.ds[0] = at(13);
+    w.s[1] = at(14);
+    w.ds[1] = at(15);
+    w.plane_stride = fb / sizeof(cx<T>);
+    return w;
+}
+// a chunk of the tangent calls holds twice the fields of a chunk of the plain step
+static long jvp_chunk_fields(const tcfd_ns2d_plan* p, long batch) {
+    const long c2 = chunk_fields(p, 2 * batch);
+    if (c2 >= 2 * batch) return batch;
+    const long c = std::max<long>(1, c2 / 2);
+    if (c >= batch) return batch;
+    const long nchunks = (batch + c - 1) / c;
+    return (batch + nchunks - 1) / nchunks;
+}
+TCFD_API size_t tcfd_ns2d_jvp_workspace_bytes(const tcfd_ns2d_plan* p, long batch) {
+    if (!p || batch <= 0) return 0;
+    return (size_t)16 * field_bytes(p, jvp_chunk_fields(p, batch));
+}
+
+// Sizes whose one-pass row kernel would need scratch memory run p and dp as two row passes: the fp64 transforms of 20
+// elements per lane (n = 5 * 2^k), where four arrays are 320 registers before the radix-20 butterfly's temporaries (one pass:
+// 128 - 692 bytes of scratch per lane; the two passes: none -- profiles/ns2d_jvp_kernel_resource_usage.txt).
+template <typename T, int N>
+static constexpr bool jvp_two_pass() {
+    return sizeof(T) == 8 && Cfg<T, N>::ROW_EPT == 20;
+}
+
+template <typename T, int N, int PART>
+static int launch_rows_jvp(const tcfd_ns2d_plan* p, const JvpWs<T>& W, long batch, hipStream_t st) {
+    constexpr int EPT = Cfg<T, N>::ROW_EPT, THR = Cfg<T, N>::ROW_THREADS;
+    using Gm = RowGeom<T, N, EPT, THR>;
+    auto kern = k_rows_jvp<T, N, EPT, THR, PART>;
+    static DevOnce lds_once;
+    if (int rc_ = set_lds(lds_once, kern, Gm::LDS_BYTES)) return rc_;
+    const long npairs = batch * (N / 2);
+    const long blocks = rows_grid(p, (npairs + Gm::GROUPS - 1) / Gm::GROUPS, 4);
+    ProfScope prof(p, 1, st);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(Gm::THREADS), Gm::LDS_BYTES, st, (const cx<T>*)W.planes,
+                       (const cx<T>*)W.dplanes, W.plane_stride, W.adv, W.dadv, (const cx<T>*)p->tw, npairs, p->ldw);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// out_f may be null (the caller wants the tangent only); out_f / out_df: caller layout (pitch m)
+template <typename T, int N>
+static int explicit_jvp_impl(const tcfd_ns2d_plan* p, const void* w, const void* dw, void* out_f, void* out_df, long batch,
+                             void* ws, hipStream_t st) {
+    constexpr int CEPT = Cfg<T, N>::COL_EPT, COLS = Cfg<T, N>::COLS;
+    JvpWs<T> W = carve_jvp<T>(p, ws, batch);
+    int rc;
+    ColArgs<T> a{};
+    a.plane_stride = W.plane_stride;
+    a.u_in_ld = p->m;
+    a.nyq = 0;    // whole-column tiles, every column present (the row pass reads the plain layout)
+    a.planes = W.planes;
+    a.u_in = (const cx<T>*)w;
+    if ((rc = launch_cols_v<T, N, MODE_A, CEPT, COLS>(p, a, batch, st))) return rc;
+    a.planes = W.dplanes;
+    a.u_in = (const cx<T>*)dw;
+    if ((rc = launch_cols_v<T, N, MODE_A, CEPT, COLS>(p, a, batch, st))) return rc;
+    if constexpr (jvp_two_pass<T, N>()) {
+        if (out_f && (rc = launch_rows_jvp<T, N, 1>(p, W, batch, st))) return rc;
+        if ((rc = launch_rows_jvp<T, N, 2>(p, W, batch, st))) return rc;
+    } else {
+        if ((rc = launch_rows_jvp<T, N, 0>(p, W, batch, st))) return rc;
+    }
+    ColArgs<T> c{};
+    if (out_f) {
+        c.in = W.adv;
+        c.out = (cx<T>*)out_f;
+        if ((rc = launch_cols_v<T, N, MODE_F, CEPT, COLS>(p, c, batch, st))) return rc;
+    }
+    c.in = W.dadv;
+    c.out = (cx<T>*)out_df;
+    return launch_cols_v<T, N, MODE_F, CEPT, COLS>(p, c, batch, st, /*no_forcing=*/true);
+}
+TCFD_DISPATCHED(explicit_jvp_dispatch,
+                (const tcfd_ns2d_plan* p, const void* w, const void* dw, void* out_f, void* out_df, long batch, void* ws,
+                 hipStream_t st),
+                (p, w, dw, out_f, out_df, batch, ws, st), (explicit_jvp_impl<T_, N_>(p, w, dw, out_f, out_df, batch, ws, st)))
+
+TCFD_API int tcfd_ns2d_explicit_terms_jvp(const tcfd_ns2d_plan* p, const void* w, const void* dw, void* out_f, void* out_df,
+                                            long batch, void* ws, size_t ws_bytes, void* stream) {
+    if (!p || !w || !dw || !out_df || batch <= 0) return fail(TCFD_EINVAL, "explicit_terms_jvp: bad argument");
+    int rc = check_ws(p, batch, ws, ws_bytes, tcfd_ns2d_jvp_workspace_bytes(p, batch));
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t esz = (p->dtype == TCFD_C128 ? 16 : 8) * (size_t)p->n * p->m;
+    const long chunk = jvp_chunk_fields(p, batch);
+    for (long b0 = 0; b0 < batch; b0 += chunk) {
+        const long nb = std::min(chunk, batch - b0);
+        const size_t o = (size_t)b0 * esz;
+        rc = explicit_jvp_dispatch(p, (const unsigned char*)w + o, (const unsigned char*)dw + o,
+                                   out_f ? (unsigned char*)out_f + o : nullptr, (unsigned char*)out_df + o, nb, ws, st);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// The stage update on the state and on the tangent in one launch: k_stage_update's arithmetic on both (the update is linear,
+// and the tangent sees no forcing).  hp / dhp null: first stage of a step (h starts from 0); h / dh null: last stage (nothing
+// reads the accumulator).  b may be u (in-place update of a state buffer: every element is read before it is written, by the
+// same thread) -- hence no __restrict__ on the state and accumulator pointers.
+template <typename T>
+__global__ __launch_bounds__(256) void k_stage_update_jvp(const cx<T>* __restrict__ f, const cx<T>* __restrict__ df,
+                                                          const cx<T>* hp, const cx<T>* dhp, const cx<T>* b, const cx<T>* db,
+                                                          const T* __restrict__ Lt, T fa, T beta, T gdt, T mu, T mud, cx<T>* h,
+                                                          cx<T>* dh, cx<T>* u, cx<T>* du, long total, long plane) {
+    for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256L) {
+        const T L = Lt[e % plane];
+        const T r = fast_rcp((T)1 - mud * L);
+        cx<T> hn = cscale(f[e], fa), dhn = cscale(df[e], fa);
+        if (hp) {
+            hn = hn + cscale(hp[e], beta);
+            dhn = dhn + cscale(dhp[e], beta);
+        }
+        const cx<T> bv = b[e], dbv = db[e];
+        const cx<T> rhs = bv + cscale(hn, gdt) + cscale(cscale(bv, L), mu);
+        const cx<T> drhs = dbv + cscale(dhn, gdt) + cscale(cscale(dbv, L), mu);
+        if (h) {
+            h[e] = hn;
+            dh[e] = dhn;
+        }
+        u[e] = cscale(rhs, r);
+        du[e] = cscale(drhs, r);
+    }
+}
+
+// `steps` steps of the schedule of tcfd_ns2d_step_imex on the pair (w, dw): per stage the sweep above, then the stage update
+template <typename T, int N>
+static int step_jvp_impl(const tcfd_ns2d_plan* p, const void* w_in, const void* dw_in, void* w_out, void* dw_out, long batch,
+                         int nstages, const double* fa, const double* beta, const double* gdt, const double* mu,
+                         const double* mud, const int* base0, int steps, void* ws, hipStream_t st) {
+    JvpWs<T> W = carve_jvp<T>(p, ws, batch);
+    const long plane = (long)N * p->m, total = batch * plane;
+    const unsigned blocks = (unsigned)std::min<long>((total + 255) / 256, 1 << 16);
+    const cx<T>* u_src = (const cx<T>*)w_in;
+    const cx<T>* du_src = (const cx<T>*)dw_in;
+    cx<T>* F = W.planes;     // plane 0 of each set: free once the row pass has run
+    cx<T>* dF = W.dplanes;
+    for (int s = 0; s < steps; ++s) {
+        const cx<T>* u0 = u_src;
+        const cx<T>* du0 = du_src;
+        for (int k = 0; k < nstages; ++k) {
+            int rc;
+            if ((rc = explicit_jvp_impl<T, N>(p, u_src, du_src, F, dF, batch, ws, st))) return rc;
+            const bool last = (s == steps - 1) && (k == nstages - 1);
+            bool u0_needed_later = false;
+            for (int k2 = k + 1; k2 < nstages; ++k2) u0_needed_later |= (base0 && base0[k2]);
+            const bool from_u0 = base0 && base0[k];
+            int d = 0;
+            if (u0_needed_later && (const cx<T>*)W.s[0] == u0) d = 1;
+            cx<T>* out = last ? (cx<T>*)w_out : W.s[d];
+            cx<T>* dout = last ? (cx<T>*)dw_out : W.ds[d];
+            const bool load_h = (k != 0), store_h = (k != nstages - 1);   // h starts from 0 every step
+            hipLaunchKernelGGL(k_stage_update_jvp<T>, dim3(blocks), dim3(256), 0, st, (const cx<T>*)F, (const cx<T>*)dF,
+                               load_h ? (const cx<T>*)W.h : nullptr, load_h ? (const cx<T>*)W.dh : nullptr,
+                               from_u0 ? u0 : u_src, from_u0 ? du0 : du_src, (const T*)p->lin, fa ? (T)fa[k] : (T)1, (T)beta[k],
+                               (T)gdt[k], (T)mu[k], mud ? (T)mud[k] : (T)mu[k], store_h ? W.h : nullptr,
+                               store_h ? W.dh : nullptr, out, dout, total, plane);
+            HIP_TRY(hipGetLastError());
+            u_src = out;
+            du_src = dout;
+        }
+    }
+    return 0;
+}
+TCFD_DISPATCHED(step_jvp_dispatch,
+                (const tcfd_ns2d_plan* p, const void* w_in, const void* dw_in, void* w_out, void* dw_out, long batch, int nstages,
+                 const double* fa, const double* beta, const double* gdt, const double* mu_num, const double* mu_den,
+                 const int* base0, int steps, void* ws, hipStream_t st),
+                (p, w_in, dw_in, w_out, dw_out, batch, nstages, fa, beta, gdt, mu_num, mu_den, base0, steps, ws, st),
+                (step_jvp_impl<T_, N_>(p, w_in, dw_in, w_out, dw_out, batch, nstages, fa, beta, gdt, mu_num, mu_den, base0, steps,
+                                       ws, st)))
+
+TCFD_API int tcfd_ns2d_step_jvp(const tcfd_ns2d_plan* p, const void* w_in, const void* dw_in, void* w_out, void* dw_out,
+                                  long batch, int nstages, const double* fa, const double* beta, const double* gdt,
+                                  const double* mu_num, const double* mu_den, const int* base0, int steps, void* ws,
+                                  size_t ws_bytes, void* stream) {
+    if (!p || !w_in || !dw_in || !w_out || !dw_out || !beta || !gdt || !mu_num) return fail(TCFD_EINVAL, "step_jvp: null argument");
+    if (batch <= 0 || steps <= 0 || nstages <= 0) return fail(TCFD_EINVAL, "step_jvp: batch/steps/nstages must be > 0");
+    if (w_out == dw_out || w_out == dw_in || dw_out == w_in)
+        return fail(TCFD_EINVAL, "step_jvp: the state and the tangent arrays must not overlap");
+    int rc = check_ws(p, batch, ws, ws_bytes, tcfd_ns2d_jvp_workspace_bytes(p, batch));
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t esz = (p->dtype == TCFD_C128 ? 16 : 8) * (size_t)p->n * p->m;
+    const long chunk = jvp_chunk_fields(p, batch);
+    for (long b0 = 0; b0 < batch; b0 += chunk) {
+        const long nb = std::min(chunk, batch - b0);
+        const size_t o = (size_t)b0 * esz;
+        rc = step_jvp_dispatch(p, (const unsigned char*)w_in + o, (const unsigned char*)dw_in + o, (unsigned char*)w_out + o,
+                               (unsigned char*)dw_out + o, nb, nstages, fa, beta, gdt, mu_num, mu_den, base0, steps, ws, st);
         if (rc) return rc;
     }
     return 0;

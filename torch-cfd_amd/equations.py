@@ -18,7 +18,8 @@ n = p * 2^k with a small odd p (48, 112, 224, ...: power-of-two HIP transforms +
 -- anything else raises.  The fused kernels are
 forward-only; when gradients are asked for (a state that requires grad, trainable
 stepper coefficients) the operator steps through ``autograd.py``: the same arithmetic
-as device tensor ops around the HIP transforms and their hand-written adjoints.
+as device tensor ops around the HIP transforms and their hand-written adjoints.  A forward-mode dual number
+(``torch.autograd.forward_ad``) as the state runs the tangent-linear kernels (``explicit_terms_jvp`` / ``tangent_step``).
 """
 from __future__ import annotations
 
@@ -28,6 +29,7 @@ import weakref
 from typing import Callable, Dict, Optional, Tuple, Union
 
 import torch
+import torch.autograd.forward_ad as fwAD
 import torch.nn as nn
 
 from . import _lib
@@ -169,6 +171,48 @@ class _HipPlan:
                                                        ws.data_ptr(), ws.numel(), self._stream())
         _lib.check(rc, "tcfd_ns2d_explicit_terms_vjp")
         return out
+
+    def jvp_workspace(self, batch: int) -> torch.Tensor:
+        """Scratch of the tangent-linear calls (``tcfd_ns2d_jvp_workspace_bytes``): the same buffer as ``workspace``, grown."""
+        if not hasattr(self.lib, "tcfd_ns2d_step_jvp"):   # added without a new ABI number: a stale library loads, but lacks them
+            raise _lib.TcfdError(f"{_lib.LIB_PATH} was built before the tangent-linear entry points (tcfd_ns2d_*_jvp) were added: "
+                                 "rebuild it with torch_cfd_amd._lib.build_library(force=True)")
+        need = self.lib.tcfd_ns2d_jvp_workspace_bytes(self.handle, batch)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def explicit_terms_jvp(self, w, dw):
+        """(F(w), F'(w) dw) in one sweep (``tcfd_ns2d_explicit_terms_jvp``)."""
+        w, batch = self._prep(w)
+        dw, _ = self._prep(dw)
+        f, df = torch.empty_like(w), torch.empty_like(w)
+        if batch == 0:
+            return f, df
+        ws = self.jvp_workspace(batch)
+        with torch.cuda.device(self.device):
+            rc = self.lib.tcfd_ns2d_explicit_terms_jvp(self.handle, w.data_ptr(), dw.data_ptr(), f.data_ptr(), df.data_ptr(),
+                                                       batch, ws.data_ptr(), ws.numel(), self._stream())
+        _lib.check(rc, "tcfd_ns2d_explicit_terms_jvp")
+        return f, df
+
+    def step_jvp(self, w, dw, beta, gdt, mu, steps: int, fa=None, mu_den=None, base0=None):
+        """``steps`` steps of the schedule of ``step`` on the state and a tangent together (``tcfd_ns2d_step_jvp``)."""
+        w, batch = self._prep(w)
+        dw, _ = self._prep(dw)
+        out, dout = torch.empty_like(w), torch.empty_like(w)
+        if batch == 0:
+            return out, dout
+        ws = self.jvp_workspace(batch)
+        ints = (ctypes.c_int * len(beta))(*[int(v) for v in base0]) if base0 is not None else None
+        with torch.cuda.device(self.device):
+            rc = self.lib.tcfd_ns2d_step_jvp(
+                self.handle, w.data_ptr(), dw.data_ptr(), out.data_ptr(), dout.data_ptr(), batch, len(beta),
+                _lib.darray(fa) if fa is not None else None, _lib.darray(beta), _lib.darray(gdt), _lib.darray(mu),
+                _lib.darray(mu_den) if mu_den is not None else None, ints, steps, ws.data_ptr(), ws.numel(), self._stream())
+        _lib.check(rc, "tcfd_ns2d_step_jvp")
+        return out, dout
 
     def stream_residual(self, w, wt, want_psi=True, want_res=True):
         w, batch = self._prep(w)
@@ -588,24 +632,84 @@ class NavierStokes2DSpectral(ImplicitExplicitODE):
         out = out.reshape(lead)
         return out, ((out - vort_hat) / (steps * dt) if want_dwdt else None)
 
+    def _schedule(self, stepper, params, dt):
+        # the coefficient tensors may live on the GPU: read them back once, not per step
+        ckey = (float(dt), id(stepper)) + tuple((k, v.data_ptr(), v._version) for k, v in params.items())
+        if self._coef_cache is None or self._coef_cache[0] != ckey:
+            self._coef_cache = (ckey, stepper.stage_schedule(params, dt))
+        return self._coef_cache[1]
+
+    # -- forward mode: the tangent-linear model on its own kernels (tcfd_ns2d_explicit_terms_jvp / tcfd_ns2d_step_jvp)
+    def _jvp_plan(self, w_hat, dw_hat, what: str) -> _HipPlan:
+        """Checks shared by the tangent-linear entry points, in the order shapes (ValueError) -> gradients -> device plan."""
+        if not (torch.is_tensor(w_hat) and torch.is_tensor(dw_hat)) or w_hat.shape != dw_hat.shape or w_hat.dtype != dw_hat.dtype:
+            raise ValueError(f"{what}: the tangent must have the shape and dtype of the state, got "
+                             f"{tuple(getattr(dw_hat, 'shape', ()))} {getattr(dw_hat, 'dtype', None)} for "
+                             f"{tuple(getattr(w_hat, 'shape', ()))} {getattr(w_hat, 'dtype', None)}")
+        n, m = self.kx.shape[-2:]
+        if not w_hat.is_complex() or w_hat.dim() < 2 or w_hat.dim() > 4 or tuple(w_hat.shape[-2:]) != (n, m):
+            raise ValueError(f"{what}: expected a complex (n, m), (B, n, m) or (B, T, n, m) half spectrum with (n, m) = "
+                             f"({n}, {m}), got {tuple(w_hat.shape)} {w_hat.dtype}")
+        if self._wants_grad(w_hat, dw_hat):
+            raise NotImplementedError(f"{what}: forward mode over reverse mode is not implemented -- the state or its tangent "
+                                      "requires grad in grad mode; detach them or differentiate with the reverse-mode path alone")
+        plan = self._plan(w_hat)
+        if not isinstance(plan, _HipPlan):
+            raise NotImplementedError(f"{what}: the tangent-linear kernels cover the fused grid sizes only (n = 2^k in 8..2048, "
+                                      f"3 * 2^k in 96..1536, 5 * 2^k in 80..1280); n = {n} runs on the composite / dense plans")
+        return plan
+
+    def _tangent_steps(self, w_hat, dw_hat, dt, steps, params, stepper):
+        plan = self._jvp_plan(w_hat, dw_hat, "tangent_step")
+        if self._wants_grad(*params.values()):
+            raise NotImplementedError("tangent_step: trainable stepper coefficients (requires_grad=True) together with a tangent "
+                                      "are not implemented; freeze the coefficients or step under torch.no_grad()")
+        if not _is_module_stepper(stepper):
+            raise NotImplementedError("tangent_step: the fused tangent-linear step needs a stepper of this module (IMEXStepper, "
+                                      "RK4CrankNicolsonStepper); a foreign solver differentiates through explicit_terms")
+        sc = self._schedule(stepper, params, dt)
+        out, dout = plan.step_jvp(w_hat, dw_hat, sc["beta"], sc["gdt"], sc["mu"], steps, fa=sc["fa"], mu_den=sc["mu_den"],
+                                  base0=sc["base0"])
+        return out.reshape(w_hat.shape), dout.reshape(w_hat.shape)
+
+    def explicit_terms_jvp(self, w_hat, dw_hat) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(F(w), F'(w) dw)``: the explicit terms and their directional derivative along ``dw_hat`` (same shape and dtype
+        as ``w_hat``), one fused sweep.  The tangent carries no forcing."""
+        f, df = self._jvp_plan(w_hat, dw_hat, "explicit_terms_jvp").explicit_terms_jvp(w_hat, dw_hat)
+        return f.reshape(w_hat.shape), df.reshape(w_hat.shape)
+
+    def tangent_step(self, w_hat, dw_hat, dt, steps=1) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``steps`` steps of the operator's stepper on the state AND on a perturbation of it: returns ``(w_new, dw_new)``
+        with ``dw_new = d(w_new)/d(w) . dw_hat`` (the tangent-linear model), all stages of all steps in one library call."""
+        if self.solver is None:
+            raise TypeError("NavierStokes2DSpectral needs a solver (e.g. RK4CrankNicolsonStepper()) to step")
+        return self._tangent_steps(w_hat, dw_hat, dt, steps, self.solver.params, self.solver)
+
     def _fused_steps(self, vort_hat, dt, steps, params=None, want_dwdt=True, stepper=None):
         stepper = self.solver if stepper is None else stepper
         if stepper is None:
             raise TypeError("NavierStokes2DSpectral needs a solver (e.g. RK4CrankNicolsonStepper()) to step")
         params = stepper.params if params is None else params
+        primal, tangent = fwAD.unpack_dual(vort_hat)
+        if tangent is not None:   # forward-mode dual number: the tangent-linear step carries it
+            out, dout = self._tangent_steps(primal, tangent, dt, steps, params, stepper)
+            new = fwAD.make_dual(out, dout)
+            if not want_dwdt:
+                return new, None
+            scale = steps * dt
+            return new, fwAD.make_dual((out - primal) / scale, (dout - tangent) / scale)
         if self._wants_grad(vort_hat, *params.values()):
             return self._autograd_steps(vort_hat, dt, steps, params, stepper, want_dwdt)
-        # the coefficient tensors may live on the GPU: read them back once, not per step
-        ckey = (float(dt), id(stepper)) + tuple((k, v.data_ptr(), v._version) for k, v in params.items())
-        if self._coef_cache is None or self._coef_cache[0] != ckey:
-            self._coef_cache = (ckey, stepper.stage_schedule(params, dt))
-        sc = self._coef_cache[1]
+        sc = self._schedule(stepper, params, dt)
         out, dwdt = self._plan(vort_hat).step(vort_hat, sc["beta"], sc["gdt"], sc["mu"], steps, 1 / (steps * dt), want_dwdt,
                                               fa=sc["fa"], mu_den=sc["mu_den"], base0=sc["base0"])
         return out.reshape(vort_hat.shape), (dwdt.reshape(vort_hat.shape) if want_dwdt else None)
 
     # -- ImplicitExplicitODE interface
     def explicit_terms(self, vort_hat):
+        primal, tangent = fwAD.unpack_dual(vort_hat)
+        if tangent is not None:
+            return fwAD.make_dual(*self.explicit_terms_jvp(primal, tangent))
         if self._wants_grad(vort_hat):
             from . import autograd as ad
 
@@ -623,7 +727,8 @@ class NavierStokes2DSpectral(ImplicitExplicitODE):
         return vort_hat / (1 - dt * self.linear_term)
 
     def residual(self, vhat: torch.Tensor, vt_hat: torch.Tensor):
-        if self._wants_grad(vhat, vt_hat):
+        dual = any(fwAD.unpack_dual(t).tangent is not None for t in (vhat, vt_hat))   # forward mode: through explicit_terms
+        if dual or self._wants_grad(vhat, vt_hat):
             return vt_hat - self.explicit_terms(vhat) - self.implicit_terms(vhat)
         _, res = self._plan(vhat).stream_residual(vhat, vt_hat, want_psi=False)
         return res.reshape(vhat.shape)
