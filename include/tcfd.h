@@ -32,6 +32,26 @@
  *     other even n is served above this boundary (dense device transforms,
  *     torch-cfd_amd/mixed_radix.py).  FNO plans: X, Y in [4, 1024] (FFT kernels for
  *     2^k, 3 * 2^k, 5 * 2^k; pruned direct DFTs otherwise, tcfd_fno_plan_supports).
+ *
+ * Memory contract (checked call by call with guarded, poisoned buffers: tests/test_memory_contract_gpu.py)
+ *   - alignment: a workspace is carved in 256-byte units from its base, so the base must be 256-byte aligned (what hipMalloc
+ *     returns).  Data pointers are tested at 256-byte alignment as well; the kernels use 16-byte vector accesses, so a
+ *     tensor that starts at a smaller alignment is outside what the tests cover.
+ *   - a *_workspace_bytes function returns exactly what its calls need: with that many bytes a call touches nothing beyond
+ *     them, with one byte less it returns TCFD_EWORKSPACE, sets tcfd_last_error and touches neither outputs nor workspace.
+ *     Every size function returns 0 for an empty batch.  The need is NOT monotonic in the batch (balanced chunks): ask for
+ *     the batch of the call.  A larger workspace is always accepted.
+ *   - the contents of a workspace on entry are arbitrary (nothing is read before the call itself has written it; no memset
+ *     is needed between calls or epochs) and unspecified on exit.
+ *   - an output is written in full -- every element -- and nothing outside it, whatever it held before; the result depends
+ *     on nothing but the inputs.  The exceptions: tcfd_data_* write nothing for a sample whose index lies outside the source;
+ *     the `partials` of tcfd_fno_pointwise_bwd / _bwd_out / _bwd_pe are an IN-OUT buffer that the caller zero-fills before the
+ *     call (see there: rows beyond dims[5] are never written, and the tiled kernel stores only the entries of a row that mean
+ *     something).  An output pointer documented as optional may be NULL.
+ *   - inputs are read only and come back unchanged; an output may alias an input only where the entry point says so.
+ *   - tcfd_irfft2 / tcfd_irfft2_subsample need only a PREFIX of tcfd_ns2d_workspace_bytes(plan, batch): one field of the
+ *     whole batch in the padded pitch, align256(batch * n * ldw * sizeof(complex)) bytes, never more than the full size.
+ *     tcfd_fvm_project likewise needs a prefix of tcfd_fvm_workspace_bytes.
  */
 #ifndef TCFD_H
 #define TCFD_H
@@ -403,7 +423,12 @@ int tcfd_fno_profile_end(int capacity, int* count, int* kinds, float* ms);
  * layer: ci):  A[o][0:ch] = dW2[o][.],  A[o][ch] = db2[o] = dbs[o],  A[o][ch+1 : ch+1+ci] = dWs[o][.];
  * B[m][0:ci] = dW1[m][.],  B[m][ci] = db1[m].  The caller sums the rows (deterministic reduction).
  * x == NULL: layout query, only dims is filled.  Replaces torch autograd through fno/base.py:86-111 +
- * fno/sfno.py:607-614.  TCFD_EINVAL for channel combinations that are not instantiated. */
+ * fno/sfno.py:607-614.  TCFD_EINVAL for channel combinations that are not instantiated.
+ * `partials` must be ZERO-FILLED by the caller (max_waves rows): a launch writes the rows of its waves only (dims[5] of them), and
+ * of such a row the tiled all-matrix-instruction kernel (tcfd_fno_pointwise_bwd_out, two-layer form, P % 4 == 0) stores exactly the
+ * entries named above -- A[o < co][0 : ch + 1] and, with a skip convolution, A[o < co][ch + 1 : ch + 1 + ci]; B[m < cm][0 : ci + 1]
+ * -- and never the padding, while the LDS-staged kernel (every other form) stores the whole row, padding as zeros.  Zero-filled
+ * beforehand, the rows can be added as they are in both cases. */
 int tcfd_fno_pointwise_bwd(const void* x, const void* skip, const void* dout, void* dx, void* dskip, const void* w1,
                            const void* b1, const void* w2t, const void* b2, const void* wst, const void* bs,
                            void* partials, int max_waves, int* dims, int batch, int ci, int cm, int co, long P, int T,

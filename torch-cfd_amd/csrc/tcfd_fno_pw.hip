@@ -547,14 +547,20 @@ __global__ __launch_bounds__(128) void k_pointwise_bwd(PwBwdArgs a) {
             }
         }
     }
-    // this wave's partial sums as row-major padded tiles:  A (COP x CB) | B (CM1 x CIP)
+    // this wave's partial sums as row-major padded tiles:  A (COP x CB) | B (CM1 x CIP).  The padding is stored as exact zeros
+    // (include/tcfd.h: "zero-padded tiles"): the LDS rows behind it are never written, so its accumulators hold whatever the
+    // workgroup found in LDS -- products that never reach a real entry (row i of the first operand only feeds row i of the tile,
+    // row j of the second only column j), but that would leave the output depending on memory the call never wrote.
     float* out = a.partials + ((size_t)blockIdx.x * Gm::WAVES + wave) * Gm::TOTAL;
 #pragma unroll
     for (int to = 0; to < TO; ++to)
 #pragma unroll
         for (int tb = 0; tb < TB; ++tb)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) out[(16 * to + 4 * kq + r) * Gm::CB + 16 * tb + kc] = accA[to * TB + tb][r];
+            for (int r = 0; r < 4; ++r) {
+                const int row = 16 * to + 4 * kq + r, col = 16 * tb + kc;
+                out[row * Gm::CB + col] = (row < CO && col < CH + 1 + CI) ? accA[to * TB + tb][r] : 0.f;
+            }
     if constexpr (HAS_L1) {
         float* o1 = out + Gm::N_A;
 #pragma unroll
@@ -562,7 +568,10 @@ __global__ __launch_bounds__(128) void k_pointwise_bwd(PwBwdArgs a) {
 #pragma unroll
             for (int ti = 0; ti < TI; ++ti)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) o1[(16 * tm + 4 * kq + r) * Gm::CIP + 16 * ti + kc] = accB[tm * TI + ti][r];
+                for (int r = 0; r < 4; ++r) {
+                    const int row = 16 * tm + 4 * kq + r, col = 16 * ti + kc;
+                    o1[row * Gm::CIP + col] = (row < CM && col < CI + 1) ? accB[tm * TI + ti][r] : 0.f;
+                }
     }
 }
 

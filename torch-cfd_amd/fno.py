@@ -939,6 +939,19 @@ def _is_pointwise(conv) -> bool:
             and conv.groups == 1 and all(s_ == 1 for s_ in conv.stride) and all(p_ == 0 for p_ in conv.padding))
 
 
+def _pointwise_operands(lin1, lin2, skip_conv):
+    """The parameter arrays of a block as the pointwise kernels take them (include/tcfd.h, tcfd_fno_pointwise):
+    ``(w1, b1, w2t, b2, wst, bs)`` -- w1 (cm, ci) as stored, w2t (cm, co) and wst (ci, co) TRANSPOSED, each contiguous; a missing
+    module or bias is None (a NULL pointer).  Shared by the float32 and float64 wrappers and by the memory-contract tests."""
+    def mat(conv, transpose):
+        w = conv.weight.detach().reshape(conv.out_channels, conv.in_channels)
+        return (w.t() if transpose else w).contiguous()
+
+    bias = lambda c: c.bias.detach().contiguous() if (c is not None and c.bias is not None) else None
+    return (mat(lin1, False) if lin1 is not None else None, bias(lin1), mat(lin2, True), bias(lin2),
+            mat(skip_conv, True) if skip_conv is not None else None, bias(skip_conv))
+
+
 def hip_pointwise(x: torch.Tensor, lin1, act1, lin2, skip=None, skip_conv=None, act2=None,
                   skip_last_slice: bool = False, norm: Optional[nn.GroupNorm] = None,
                   out: Optional[torch.Tensor] = None, pre: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
@@ -1008,12 +1021,7 @@ def hip_pointwise(x: torch.Tensor, lin1, act1, lin2, skip=None, skip_conv=None, 
                             or not pre.is_contiguous() or norm is not None):
         raise ValueError("pre must be a contiguous float32 tensor of the block's output shape on x's device (no folded LayerNorm)")
 
-    def mat(conv, transpose):
-        w = conv.weight.detach().reshape(conv.out_channels, conv.in_channels)
-        return (w.t() if transpose else w).contiguous()
-
-    w1 = mat(lin1, False) if lin1 is not None else None
-    w2t = mat(lin2, True)
+    w1, b1, w2t, b2, wst, bs = _pointwise_operands(lin1, lin2, skip_conv)
     w2_bs = b2_bs = 0
     folded_bias = None
     if norm is not None:
@@ -1039,10 +1047,7 @@ def hip_pointwise(x: torch.Tensor, lin1, act1, lin2, skip=None, skip_conv=None, 
             folded_bias = folded_bias + lin2.bias.detach().double()[None]
         folded_bias = folded_bias.float().contiguous()                                              # (b, co)
         w2_bs, b2_bs = ci * co, co
-    wst = mat(skip_conv, True) if skip_conv is not None else None
     ptr = lambda t: t.data_ptr() if t is not None else None
-    bias = lambda c: c.bias.detach().contiguous() if (c is not None and c.bias is not None) else None
-    b1, b2, bs = bias(lin1), bias(lin2), bias(skip_conv)
     if folded_bias is not None:
         b2 = folded_bias
     lib = _lib.load()
@@ -1081,12 +1086,7 @@ def _hip_pointwise_f64(x, lin1, c1, lin2, skip, skip_conv, c2, skip_last_slice, 
         mode, s_t, sT = 2, skip.detach().contiguous(), skip.shape[-1]
     x = x.detach().contiguous()
     out = torch.empty(b, co, *x.shape[2:], dtype=torch.float64, device=x.device)
-    mat = lambda conv, tr: (lambda w: (w.t() if tr else w).contiguous())(conv.weight.detach().reshape(conv.out_channels, conv.in_channels))
-    w1 = mat(lin1, False) if lin1 is not None else None
-    w2t = mat(lin2, True)
-    wst = mat(skip_conv, True) if skip_conv is not None else None
-    bias = lambda c: c.bias.detach().contiguous() if (c is not None and c.bias is not None) else None
-    b1, b2, bs = bias(lin1), bias(lin2), bias(skip_conv)
+    w1, b1, w2t, b2, wst, bs = _pointwise_operands(lin1, lin2, skip_conv)
     lib = _lib.load()
     stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
     w2_bs = b2_bs = 0
