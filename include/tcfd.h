@@ -28,9 +28,13 @@
  *     at plan creation, and frozen in the plan.
  *   - complex data are interleaved (re, im) pairs of the plan's real type,
  *     half spectra are (batch, n, m) row-major with m = n/2 + 1.  Solver plans:
- *     n = 2^k (8 ... 2048), 3 * 2^k (96 ... 1536) or 5 * 2^k (80 ... 1280); every
+ *     n = 2^k (8 ... 4096), 3 * 2^k (96 ... 1536) or 5 * 2^k (80 ... 1280); every
  *     other even n is served above this boundary (dense device transforms,
- *     torch-cfd_amd/mixed_radix.py).  FNO plans: X, Y in [4, 1024] (FFT kernels for
+ *     torch-cfd_amd/mixed_radix.py).  n = 4096 was ADDED under revision 13 without a
+ *     new number: a library built before it answers TCFD_EINVAL from
+ *     tcfd_ns2d_plan_create.  One call takes at most (2^31 - 1) / (n + 18) fields
+ *     (the launch grids are 32-bit; 521 997 at n = 4096): a larger batch is
+ *     TCFD_EINVAL, never wrapped.  FNO plans: X, Y in [4, 1024] (FFT kernels for
  *     2^k, 3 * 2^k, 5 * 2^k; pruned direct DFTs otherwise, tcfd_fno_plan_supports).
  *
  * Memory contract (checked call by call with guarded, poisoned buffers: tests/test_memory_contract_gpu.py)
@@ -118,7 +122,7 @@ void tcfd_ns2d_plan_destroy(tcfd_ns2d_plan* plan);
 int tcfd_ns2d_plan_info(const tcfd_ns2d_plan* plan, int* separable, int* sparse_forcing, int* keep_cols);
 
 /* Which kernel variants the plan launches: split = 1 when the column transform is cut radix-2 across the
- * row pass; rows_kernel = 6 (LDS-DMA staged row pass), 5 (register staged) or 4 (round-1 kernel). */
+ * row pass (default at n = 1024 and n = 4096); rows_kernel = 5 (register staged) or 7 (cross-lane transforms, n = 1024). */
 int tcfd_ns2d_plan_variant(const tcfd_ns2d_plan* plan, int* split, int* rows_kernel);
 
 /* How a batched call on this plan is cut into chunks: `*fields_per_chunk` = batch elements per chunk for a call with
@@ -136,7 +140,10 @@ int tcfd_debug_xl_fft1024(const tcfd_ns2d_plan* plan, const void* in, void* out,
 
 /* Bytes of caller-owned scratch needed by the calls below for `batch` fields.  Batched calls run in cache-sized chunks
  * through one chunk-sized set of fields, so this stops growing with the batch at one chunk (plus one field of the whole
- * batch for tcfd_irfft2): 0.55 GB at 1024^2 x 64 complex128. */
+ * batch for tcfd_irfft2): 0.55 GB at 1024^2 x 64 complex128.  The chunk (tcfd_ns2d_plan_chunking): as many fields as have
+ * their 7-field working set inside the last-level cache; where fewer than three fit, ONE field at n = 2048, FOUR at n = 4096
+ * (nothing of a 4096^2 sample stays in the cache; 8 x 4 fields: 4.3 GB complex128 / 2.2 GB complex64 from batch 4 up) and
+ * the whole batch at n = 1280, 1536 in complex128 (8 fields of the whole batch). */
 size_t tcfd_ns2d_workspace_bytes(const tcfd_ns2d_plan* plan, long batch);
 
 /* ---- RK4-CN time stepping ----------------------------------------------------
@@ -195,7 +202,7 @@ int tcfd_ns2d_explicit_terms_vjp(const tcfd_ns2d_plan* plan, const void* w, cons
  * fields, h and dh, two intermediate states each); the calls run chunk by chunk, a chunk holding half the batch elements of a
  * chunk of tcfd_ns2d_step, so it stops growing at one chunk -- except where tcfd_ns2d_step itself runs the whole batch at once
  * (fewer than three fields per cache-sized chunk and n < 2048: n = 1280, 1536 in complex128), where it is 16 fields of the
- * whole batch.  No atomics: two runs give the same bits. */
+ * whole batch.  At n = 2048 a chunk is one sample (16 fields of it), at n = 4096 two (4.3 GB complex128).  No atomics: two runs give the same bits. */
 size_t tcfd_ns2d_jvp_workspace_bytes(const tcfd_ns2d_plan* plan, long batch);
 int tcfd_ns2d_explicit_terms_jvp(const tcfd_ns2d_plan* plan, const void* w, const void* dw, void* out_f, void* out_df,
                                  long batch, void* workspace, size_t workspace_bytes, void* stream);

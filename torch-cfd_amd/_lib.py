@@ -74,7 +74,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
 # compile jobs: (source, extra flags, object).  tcfd_ns2d.hip is compiled twice -- unit 0 = C ABI + float64 kernels, unit 1 =
 # float32 kernels -- and the FNO kernels are three files (transforms + contraction / pointwise block / tiled backward; the tiled
 # backward twice: unit 0 = the SFNO's blocks, unit 1 = the FNO3d baseline's), so that
-# the hipcc processes take ~3.5 minutes side by side instead of 7 + 5 one after the other.  tcfd_fvm.hip (finite-volume solver) is
+# the hipcc processes take ~4.5 minutes side by side (3.5 before the 4096-point instantiations) instead of one after the other.  tcfd_fvm.hip (finite-volume solver) is
 # compiled twice the same way: unit 0 = C ABI + float64 kernels, unit 1 = float32 kernels.
 JOBS = (("tcfd_ns2d.hip", ("-DTCFD_UNIT=0",), "tcfd_ns2d.o"),
         ("tcfd_ns2d.hip", ("-DTCFD_UNIT=1",), "tcfd_ns2d_f32.o"),

@@ -101,6 +101,11 @@ TCFD_CFG(float, 256, 16, 16, 16, 256)
 TCFD_CFG(float, 512, 8, 16, 8, 256)
 TCFD_CFG(float, 1024, 16, 8, 16, 256)
 TCFD_CFG(float, 2048, 16, 8, 16, 256)
+// n = 4096: the step runs split (2048-point half columns in the tile forms of the two rows above); these whole-column tiles
+// serve the passes that are never split (plain transforms, the VJP / JVP sweeps) and TCFD_SPLIT=0.  One (two) columns: the
+// fp64 tile is 64 KB + 96 KB of row tables = the CU's whole LDS, the fp32 one 112 KB (four columns would be 176 KB)
+TCFD_CFG(double, 4096, 16, 1, 16, 256)
+TCFD_CFG(float, 4096, 16, 2, 16, 256)
 // n = 3 * 2^k: twelve elements per lane (radix 12 = 4 x 3 in registers, then radix-4 passes), plain Stockham tiles
 TCFD_CFG(double, 96, 12, 32, 12, 256)
 TCFD_CFG(double, 192, 12, 16, 12, 256)
@@ -191,7 +196,7 @@ struct ColArgs {
     int nt_planes; // plane stores with the non-temporal hint (small cache-resident problems, see launch_cols)
     int nt_out;    // MODE_C: the new state and dw/dt go to the CALLER's arrays and are not read again by this call -- stored with
                    // the non-temporal hint they do not push the next chunk's working set out of the Infinity Cache
-    int pair_xcd;  // block->tile map: 0 = batch fastest; LG = 2 / 4: the LG tiles that share a 128-byte line on one XCD
+    int pair_xcd;  // block->tile map: 0 = batch fastest; LG = 2 / 4 / 8: the LG tiles that share a 128-byte line on one XCD
     cx<T>* h_out;  // RK accumulator write (NULL: == h)
 };
 
@@ -1321,7 +1326,7 @@ struct Tuning {
     int cols_lds_pad;        // TCFD_COLS_LDS_PAD: extra dynamic LDS bytes of the column kernels (experiments)
     int rows7_minw;          // TCFD_ROWS7_MINW: waves per SIMD of the fp32 cross-lane row kernel (2 / 4)
     int rows_blocks_per_cu;  // TCFD_ROWS_BLOCKS_PER_CU: persistent row-pass grid
-    int pair_xcd;            // TCFD_PAIR_XCD: put the 2 / 4 column tiles that share a 128-byte line on one XCD (0 off, 2 pairs only)
+    int pair_xcd;            // TCFD_PAIR_XCD: put the 2 / 4 column tiles that share a 128-byte line on one XCD (0 off, 2 pairs only, 4 at most four, 8 always eight)
     int ablate;              // TCFD_ABLATE: timing ablations (results are WRONG when non-zero)
     int nt_planes;           // TCFD_NT_PLANES: non-temporal plane stores (-1: for the small-tile launches only)
     int rows_v;              // TCFD_ROWS_V: 0 = per size; 5 = register-staged rows with Stockham exchanges, 7 = cross-lane
@@ -1368,7 +1373,7 @@ struct tcfd_ns2d_plan {
 };
 
 static bool supported_n(int n) {
-    return (n >= 8 && n <= 2048 && (n & (n - 1)) == 0) || n == 96 || n == 192 || n == 384 || n == 768 ||   // 2^k, 3 * 2^k
+    return (n >= 8 && n <= 4096 && (n & (n - 1)) == 0) || n == 96 || n == 192 || n == 384 || n == 768 ||   // 2^k, 3 * 2^k
            n == 1536 || n == 80 || n == 160 || n == 320 || n == 640 || n == 1280;                         // and 5 * 2^k
 }
 
@@ -1564,7 +1569,7 @@ static int fill_round_fields(tcfd_ns2d_plan* p);   // (needs the size dispatch, 
 TCFD_API int tcfd_ns2d_plan_create(tcfd_ns2d_plan** out, int n, int dtype, const double* kx, const double* ky,
                                      const double* linear_term, const double* mask, const double* forcing_hat) {
     if (!out || !kx || !ky || !linear_term || !mask) return fail(TCFD_EINVAL, "plan_create: null argument");
-    if (!supported_n(n)) return fail(TCFD_EINVAL, "plan_create: n=%d is not a power of two in [8, 2048] (or 3 * 2^k in 96..1536, 5 * 2^k in 80..1280)", n);
+    if (!supported_n(n)) return fail(TCFD_EINVAL, "plan_create: n=%d is not a power of two in [8, 4096] (or 3 * 2^k in 96..1536, 5 * 2^k in 80..1280)", n);
     if (dtype != TCFD_C64 && dtype != TCFD_C128) return fail(TCFD_EINVAL, "plan_create: bad dtype %d", dtype);
     tcfd_ns2d_plan* p = new tcfd_ns2d_plan();   // value-initialised: every pointer / flag starts at zero
     p->n = n;
@@ -1599,8 +1604,10 @@ TCFD_API int tcfd_ns2d_plan_create(tcfd_ns2d_plan** out, int n, int dtype, const
         return rc;
     }
     (void)fill_round_fields(p);
+    // (one-column tiles -- 4096^2 fp64 with TCFD_SPLIT=0 -- cannot pack: tile 0 builds Z in TWO columns' worth of exchange buffer)
+    const bool one_column_tiles = n == 4096 && dtype == TCFD_C128 && p->tune.split == 0;
     p->nyq = (p->tune.nyq_pack && n >= 64 && (n & (n - 1)) == 0 && p->keep_cols > 0 && p->keep_cols <= p->m - 1 &&
-              true) ? 1 : 0;
+              !one_column_tiles) ? 1 : 0;
     // per pass (TCFD_NYQ_PACK = 3: the opening pass of a call only, for A/B runs; the row pass reads either form)
     p->nyq_a = p->nyq;
     p->nyq_ca = p->nyq && p->tune.nyq_pack != 3;
@@ -1675,7 +1682,11 @@ template <typename T, int C>
 static int line_group(const tcfd_ns2d_plan* p) {
     constexpr int bytes = C * (int)sizeof(cx<T>);
     if (bytes >= 128 || p->tune.pair_xcd == 0) return 0;
-    const int lg = 128 / bytes > 4 ? 4 : 128 / bytes;
+    // 16-byte tiles (the whole-column tiles of n = 4096, no other size has them): all eight of a line; TCFD_PAIR_XCD = 4 keeps four
+    // TCFD_PAIR_XCD = 8 groups eight tiles of ANY narrow width (two lines of 32-byte tiles): the same block -> tile map, reachable at
+    // the small sizes where a test of its indexing costs milliseconds
+    if (p->tune.pair_xcd == 8) return 8;
+    const int lg = 128 / bytes > 4 ? ((bytes == 16 && p->tune.pair_xcd != 4) ? 8 : 4) : 128 / bytes;
     return p->tune.pair_xcd == 2 ? 2 : lg;
 }
 
@@ -1727,7 +1738,9 @@ static int launch_cols_v(const tcfd_ns2d_plan* p, ColArgs<T> a, long batch, hipS
         HIP_TRY(hipGetLastError());
         return 0;
     };
-    constexpr bool NYQ_MODE = (MODE == MODE_A || MODE == MODE_CA || MODE == MODE_C);
+    // the packed Nyquist column needs tiles of two columns or more (emit_planes: S0 and SZ are NT elements each of the exchange buffer)
+    constexpr bool NYQ_MODE = (MODE == MODE_A || MODE == MODE_CA || MODE == MODE_C) && C >= 2;
+    if (a.nyq && !NYQ_MODE) return fail(TCFD_EINVAL, "packed Nyquist column on a column pass that cannot carry it");
     // 512-point tiles of 8 columns (1024^2 split plans and 512^2, fp64): cross-lane transforms unless TCFD_COLS_XL=0
     constexpr bool XL_OK = (NT == 512 && EPT == 8 && C == 8 && MODE != MODE_FWD && MODE != MODE_INV);
     if constexpr (XL_OK) {
@@ -1762,7 +1775,9 @@ static bool use_split(const tcfd_ns2d_plan* p) {
     const int force = p->tune.split;
     if (N < 16 || !is_pow2c(N)) return false;   // n = 3 * 2^k / 5 * 2^k: whole-column tiles only (split measured slower at 768: 160 vs 181 steps/s)
     if (force >= 0) return force != 0;
-    return N == 1024;   // (768: split 160 vs plain 181 steps/s at one round of workgroups per launch)   // fp64: 7.99 vs 8.6 ms/step; fp32 (16-column, 128-byte tiles of 512 rows): 5.61 vs 6.05 ms/step
+    // 4096: whole-column tiles are one (fp64) / two (fp32) columns wide -- 16 bytes of every row -- and fill the LDS with one
+    // workgroup per CU; the 2048-point halves are the tiles of n = 2048 (2 / 8 columns)
+    return N == 1024 || N == 4096;   // (768: split 160 vs plain 181 steps/s at one round of workgroups per launch)   // fp64: 7.99 vs 8.6 ms/step; fp32 (16-column, 128-byte tiles of 512 rows): 5.61 vs 6.05 ms/step
 }
 
 template <typename T, int N, int MODE>
@@ -2276,6 +2291,7 @@ static int irfft2_sub_impl(const tcfd_ns2d_plan* p, const void* xh, void* out, l
         case 512: { constexpr int N_ = 512; return CALL; }                \
         case 1024: { constexpr int N_ = 1024; return CALL; }              \
         case 2048: { constexpr int N_ = 2048; return CALL; }              \
+        case 4096: { constexpr int N_ = 4096; return CALL; }              \
         case 96: { constexpr int N_ = 96; return CALL; }                  \
         case 192: { constexpr int N_ = 192; return CALL; }                \
         case 384: { constexpr int N_ = 384; return CALL; }                \
@@ -2320,7 +2336,19 @@ static int irfft2_sub_impl(const tcfd_ns2d_plan* p, const void* xh, void* out, l
     }
 #endif
 
+// Largest batch of one call: the launch grids and the block -> tile maps of the column kernels (ColArgs::batch, ntiles) are
+// 32-bit.  A column grid is at most 2 (parities) x (batch x tiles rounded up to 8 line groups) <= batch (2 m + 16) workgroups
+// with one-column tiles, a row grid batch n / 2: batch (n + 18) < 2^31 keeps every one of them, and every product of two of
+// those ints, in range (n = 4096: 521 997 fields -- 70 TB of fp64 state, so memory ends a batch long before; element and byte
+// offsets are size_t / long throughout).  Larger batches are refused, never wrapped.
+static long max_batch(const tcfd_ns2d_plan* p) { return 2147483647L / (p->n + 18); }
+static int check_batch(const tcfd_ns2d_plan* p, long batch) {
+    if (batch > max_batch(p))
+        return fail(TCFD_EINVAL, "batch %ld exceeds the largest batch of one call at n = %d (%ld fields)", batch, p->n, max_batch(p));
+    return 0;
+}
 static int check_ws(const tcfd_ns2d_plan* p, long batch, void* ws, size_t bytes, size_t need) {
+    if (int rc = check_batch(p, batch)) return rc;
     if (!ws || bytes < need) return fail(TCFD_EWORKSPACE, "workspace %zu B < required %zu B", bytes, need);
     return 0;
 }
@@ -2369,7 +2397,14 @@ static long chunk_fields(const tcfd_ns2d_plan* p, long batch) {
         // most of its working set (237 of 244 MB) still fits: 16 fields 12.8 -> 11.5 ms per step with single-field chunks; at
         // 1536^2 / 1280^2 (1 - 2 fields would fit, 194 / 162 workgroups per field) the whole batch at once is faster
         // (6.3 vs 7.9 ms, 9.3 vs 13.0 ms: tests/micro/n2048_chunk.py)
-        if (c < 3) return (c >= 1 && p->n >= 2048) ? 1 : batch;
+        // 4096^2: not even one field's working set fits (7 fields = 940 MB fp64 / 473 MB fp32, c = 0), so nothing of a chunk stays on
+        // die whatever its size.  Four fields per chunk: measured at 4096^2 x 4 (tests/bench_ns2d_large.py, profiles/
+        // ns2d_large_bench.json) the four fields in every launch step in 13.06 ms fp64 against 13.76 one field at a
+        // time (a field is 4 - 8 rounds of column workgroups: longer launches amortise their tails and the launch gaps); fp32
+        // shows no preference (7.91 vs 7.68 ms, the sign changing between runs).  Beyond four the scratch would grow with the
+        // batch: 8 fields of the chunk, 4.3 GB fp64 at four
+        if (c < 3 && p->n >= 4096) c = 4;
+        else if (c < 3) return (c >= 1 && p->n >= 2048) ? 1 : batch;
         if (p->tune.round_fields > 0 && c > p->tune.round_fields) c = c / p->tune.round_fields * p->tune.round_fields;   // whole rounds
     }
     if (c >= batch) return batch;
@@ -2774,6 +2809,7 @@ static int velocity_impl(const tcfd_ns2d_plan* p, const void* w, void* uh, void*
 TCFD_API int tcfd_ns2d_velocity(const tcfd_ns2d_plan* p, const void* w, void* uh, void* vh, void* psi, long batch,
                                   void* stream) {
     if (!p || !w || batch <= 0) return fail(TCFD_EINVAL, "velocity: bad argument");
+    if (int rc = check_batch(p, batch)) return rc;
     hipStream_t st = (hipStream_t)stream;
     return p->dtype == TCFD_C128 ? velocity_impl<double>(p, w, uh, vh, psi, batch, st)
                                  : velocity_impl<float>(p, w, uh, vh, psi, batch, st);
@@ -2851,6 +2887,7 @@ TCFD_API int tcfd_irfft2_subsample(const tcfd_ns2d_plan* p, const void* xh, void
 
 TCFD_API int tcfd_rfft2(const tcfd_ns2d_plan* p, const void* x, void* out, long batch, void* stream) {
     if (!p || !x || !out || batch <= 0) return fail(TCFD_EINVAL, "rfft2: bad argument");
+    if (int rc = check_batch(p, batch)) return rc;
     return rfft2_dispatch(p, x, out, batch, (hipStream_t)stream);
 }
 
@@ -3441,6 +3478,7 @@ TCFD_API int tcfd_ns2d_refine(const tcfd_ns2d_plan* p, const void* w, const void
                               size_t ws_bytes, void* stream) {
 #if TCFD_UNIT != 1
     if (!p || !w || batch <= 0 || nt <= 0 || dt == 0.0) return fail(TCFD_EINVAL, "refine: bad argument");
+    if (int rc_ = check_batch(p, batch * nt)) return rc_;   // every (sample, step) slice is one field of the sweeps
     int rc = check_ws(p, batch, ws, ws_bytes, tcfd_ns2d_refine_workspace_bytes(p, batch, nt));
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -3458,6 +3496,7 @@ TCFD_API int tcfd_ns2d_refine_vjp(const tcfd_ns2d_plan* p, const void* w, const 
 #if TCFD_UNIT != 1
     if (!p || !w || batch <= 0 || nt <= 0 || dt == 0.0) return fail(TCFD_EINVAL, "refine_vjp: bad argument");
     if (grad_f_hat && !f_hat) return fail(TCFD_EINVAL, "refine_vjp: grad_f_hat needs f_hat");
+    if (int rc_ = check_batch(p, batch * nt)) return rc_;
     int rc = check_ws(p, batch, ws, ws_bytes, tcfd_ns2d_refine_workspace_bytes(p, batch, nt));
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;

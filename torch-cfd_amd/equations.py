@@ -13,7 +13,7 @@ but ``NavierStokes2DSpectral.forward`` / ``explicit_terms`` / ``residual`` run t
 hand-written gfx950 kernels of ``csrc/tcfd_ns2d.hip`` through the C ABI in
 ``include/tcfd.h`` (three launches per RK stage instead of ~40 ATen launches).
 There is no CPU or eager fallback: tensors must live on a HIP device and the grid
-must be square with n = 2^k (8..2048), n = 3 * 2^k (96..1536) or n = 5 * 2^k (80..1280) -- the fused kernels -- or another
+must be square with n = 2^k (8..4096), n = 3 * 2^k (96..1536) or n = 5 * 2^k (80..1280) -- the fused kernels -- or another
 n = p * 2^k with a small odd p (48, 112, 224, ...: power-of-two HIP transforms + tensor ops, ``mixed_radix.py``)
 -- anything else raises.  The fused kernels are
 forward-only; when gradients are asked for (a state that requires grad, trainable
@@ -85,6 +85,11 @@ class _HipPlan:
                 ctypes.byref(handle), n, _lib.TCFD_C128 if cdtype == torch.complex128 else _lib.TCFD_C64,
                 _lib.dptr_of_tensor(kx1d), _lib.dptr_of_tensor(ky1d), _lib.dptr_of_tensor(lin),
                 _lib.dptr_of_tensor(msk), fptr)
+        if rc == -1 and n == 4096:   # TCFD_EINVAL; the size was added without a new ABI number: a library built before it loads, and refuses the size
+            msg = self.lib.tcfd_last_error()
+            raise _lib.TcfdError(f"tcfd_ns2d_plan_create refused n = 4096 ({msg.decode() if msg else rc}): {_lib.LIB_PATH} was built "
+                                 "before the 4096-point kernels were added -- rebuild it with "
+                                 "torch_cfd_amd._lib.build_library(force=True)")
         _lib.check(rc, "tcfd_ns2d_plan_create")
         self.handle = handle
         self._ws: Optional[torch.Tensor] = None
@@ -313,15 +318,15 @@ def _composite_plan(op, n: int, cdtype, device, forcing_hat=None):
         return TensorOpPlan(op, CompositeFft(n, p_, fft_plan(m_, cdtype, device)), device, forcing_hat)
     if n % 2 or n < 4 or n > 4096:
         raise _lib.TcfdError(f"n = {n}: the HIP spectral path covers even n (the reference's irfft2 default size, "
-                             "torch_cfd/equations.py:413-422): 2^k, 3 * 2^k, 5 * 2^k on the fused kernels, the rest up to 4096 "
+                             "torch_cfd/equations.py:413-422): 2^k up to 4096, 3 * 2^k, 5 * 2^k on the fused kernels, the rest up to 4096 "
                              "through composite / dense transforms")
     return TensorOpPlan(op, DenseDft(n, cdtype), device, forcing_hat)
 
 
 def _is_pow2(n: int) -> bool:
-    """Grids the FUSED kernels cover: n = 2^k (8..2048), n = 3 * 2^k (96..1536: radix-12 first pass) and n = 5 * 2^k
+    """Grids the FUSED kernels cover: n = 2^k (8..4096), n = 3 * 2^k (96..1536: radix-12 first pass) and n = 5 * 2^k
     (80..1280: radix 20)."""
-    return (8 <= n <= 2048 and (n & (n - 1)) == 0) or n in (96, 192, 384, 768, 1536, 80, 160, 320, 640, 1280)
+    return (8 <= n <= 4096 and (n & (n - 1)) == 0) or n in (96, 192, 384, 768, 1536, 80, 160, 320, 640, 1280)
 
 
 def _plan_for_mesh(kx: torch.Tensor, ky: torch.Tensor, like: torch.Tensor):
@@ -655,7 +660,7 @@ class NavierStokes2DSpectral(ImplicitExplicitODE):
                                       "requires grad in grad mode; detach them or differentiate with the reverse-mode path alone")
         plan = self._plan(w_hat)
         if not isinstance(plan, _HipPlan):
-            raise NotImplementedError(f"{what}: the tangent-linear kernels cover the fused grid sizes only (n = 2^k in 8..2048, "
+            raise NotImplementedError(f"{what}: the tangent-linear kernels cover the fused grid sizes only (n = 2^k in 8..4096, "
                                       f"3 * 2^k in 96..1536, 5 * 2^k in 80..1280); n = {n} runs on the composite / dense plans")
         return plan
 
