@@ -708,6 +708,28 @@ __device__ __forceinline__ void xl_twiddle(cx<T> (&x)[8], cx<T> w) {
         if (b + 1 < NBITS) w = csquare(w);
     }
 }
+
+// ---- direct twiddles (fp64 column tiles) -------------------------------------------------------------------------
+// The squaring chain above costs 12 products + 2 squarings for a 3-bit digit; with a table every register gets exactly ONE
+// product with its own root (7 products) and one rounding instead of up to three.  Tables are laid out digit-major
+// ([d][lane constant]).  Used where it measured faster: the second stage of xl_col_fft512 (see there).
+// x w (DIR < 0) or x conj(w) (DIR > 0) for a forward-sign root w: the conjugate rides on the signs of the products
+template <int DIR, typename T>
+__device__ __forceinline__ cx<T> xl_cmul(cx<T> x, cx<T> w) {
+    if constexpr (DIR > 0) return mk<T>(x.x * w.x + x.y * w.y, x.y * w.x - x.x * w.y);
+    else return cmul(x, w);
+}
+// x[t] *= tab[d * STRIDE], d = digit of t over NBITS register bits from SHIFT; `tab` already points at the lane's column
+template <int DIR, int NBITS, int SHIFT, int STRIDE, typename T>
+__device__ __forceinline__ void xl_twiddle_tab(cx<T> (&x)[8], const cx<T>* tab) {
+#pragma unroll
+    for (int d = 1; d < (1 << NBITS); ++d) {
+        const cx<T> w = tab[d * STRIDE];
+#pragma unroll
+        for (int t = 0; t < 8; ++t)
+            if (((t >> SHIFT) & ((1 << NBITS) - 1)) == d) x[t] = xl_cmul<DIR>(x[t], w);
+    }
+}
 template <int DIR, typename T>
 __device__ __forceinline__ void xl_radix4_pairs(cx<T> (&x)[8]) {   // radix 4 over (t2 t1), for t0 = 0 and 1
 #pragma unroll
@@ -789,16 +811,40 @@ namespace tcfd {
 // the caller simply stores (DIR = +1) or loads (DIR = -1, the transposed flow graph) its rows at that index -- both
 // sides of the transform stay in natural order in memory.  tests/micro/xcol_fft_model.py is the numpy model.
 // =====================================================================================================
+// Direct twiddles of the column tiles (fp64, see xl_twiddle_tab): stage two (8 x 8 distinct roots W_512^(8 d m)) from a 1 KB
+// LDS table the workgroup fills once.  Stage one keeps its squaring chain: W_512^(d j) has 64 x 7 values -- 7 KB where a
+// tile has 4 KB of LDS left -- and read from the root table in memory (all seven ahead of the butterflies, or pinned two at
+// a time) the 128-register kernels go to scratch.  TCFD_XL_COL_DIRECT=0: squaring chains in both stages; fp32 keeps them.
+#ifndef TCFD_XL_COL_DIRECT
+#define TCFD_XL_COL_DIRECT 1
+#endif
 template <typename T>
+constexpr bool xl_col_direct() { return TCFD_XL_COL_DIRECT && sizeof(T) == 8; }
+constexpr int XL_COL_TAB_ELEMS = 8 * 8;   // [d][m] = W_512^(8 d m)
+// per-thread twiddles of a column transform: the first-stage root, and for the second stage either its root (squaring
+// chains) or the lane's column of the workgroup's LDS table (entry d at [8 d])
+template <typename T, bool TAB = xl_col_direct<T>()>
 struct XlColTw {
     cx<T> w1;   // W_512^j
     cx<T> w2;   // W_512^(8 (j & 7))
 };
 template <typename T>
-__device__ __forceinline__ XlColTw<T> xl_col_load_tw(const cx<T>* __restrict__ tw512, int j) {
+struct XlColTw<T, true> {
+    cx<T> w1;
+    const cx<T>* t2;
+};
+// the workgroup's stage-two table; the caller's next barrier makes it readable
+template <typename T>
+__device__ __forceinline__ void xl_col_fill_tab(cx<T>* tab, const cx<T>* __restrict__ tw512, int tid) {
+    if (tid < XL_COL_TAB_ELEMS) tab[tid] = tw512[8 * (tid >> 3) * (tid & 7)];
+}
+// `tab`: the workgroup's stage-two table (read only where the type takes table twiddles)
+template <typename T>
+__device__ __forceinline__ XlColTw<T> xl_col_load_tw(const cx<T>* __restrict__ tw512, int j, const cx<T>* tab) {
     XlColTw<T> r;
     r.w1 = tw512[j];
-    r.w2 = tw512[8 * (j & 7)];
+    if constexpr (xl_col_direct<T>()) r.t2 = tab + (j & 7);
+    else r.w2 = tw512[8 * (j & 7)];
     return r;
 }
 __device__ __forceinline__ int xl_col_row(int j) { return ((j & 7) << 3) | (j >> 3); }
@@ -808,6 +854,10 @@ __device__ __forceinline__ void xl_col_fft512(cx<T> (&x)[8], cx<T>* lds, const X
     const int wave = tid >> 6, lane = tid & 63;
     cx<T>* by_reg_wave = lds + wave * 64 + lane;          // slot (q = register, a = wave): + 512 q
     cx<T>* by_wave_reg = lds + wave * 512 + lane;         // slot (q = wave, a = register): + 64 a
+    auto twiddle2 = [&]() {
+        if constexpr (xl_col_direct<T>()) xl_twiddle_tab<DIR, 3, 0, 8>(x, tw.t2);
+        else xl_twiddle<DIR, 3, 0>(x, tw.w2);
+    };
     if constexpr (DIR > 0) {
         Dft<8, DIR, T>::run(x);
         xl_twiddle<DIR, 3, 0>(x, tw.w1);
@@ -818,7 +868,7 @@ __device__ __forceinline__ void xl_col_fft512(cx<T> (&x)[8], cx<T>* lds, const X
         for (int a = 0; a < 8; ++a) x[a] = by_wave_reg[64 * a];
         __syncthreads();
         Dft<8, DIR, T>::run(x);
-        xl_twiddle<DIR, 3, 0>(x, tw.w2);
+        twiddle2();
         xtranspose<2, 5>(x);
         xtranspose<1, 4>(x);
         xtranspose<0, 3>(x);
@@ -828,7 +878,7 @@ __device__ __forceinline__ void xl_col_fft512(cx<T> (&x)[8], cx<T>* lds, const X
         xtranspose<0, 3>(x);
         xtranspose<1, 4>(x);
         xtranspose<2, 5>(x);
-        xl_twiddle<DIR, 3, 0>(x, tw.w2);
+        twiddle2();
         Dft<8, DIR, T>::run(x);
 #pragma unroll
         for (int a = 0; a < 8; ++a) by_wave_reg[64 * a] = x[a];

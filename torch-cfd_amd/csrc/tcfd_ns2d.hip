@@ -220,11 +220,27 @@ struct ColTw {
         if constexpr (RT) load_pass_tw<T, NT, EPT>(w, tw, j);
     }
 };
+// LDS of a column workgroup behind the exchange tile: the row tables rt_kx, rt_lin, rt_mask (NT reals each), then -- cross-lane
+// tiles with table twiddles only -- the XL_COL_TAB_ELEMS stage-two roots.  The kernel, col_fft and the launcher all take the
+// layout from here.
+constexpr int COL_ROW_TABLES = 3;
+template <typename T, int NT, int EPT, int C>
+__device__ __forceinline__ T* col_row_tables(cx<T>* lds) { return reinterpret_cast<T*>(lds + lds_elems<NT, EPT, C, false>()); }
+template <typename T, int NT, int EPT, int C>
+__device__ __forceinline__ cx<T>* col_xl_tab(cx<T>* lds) {
+    return reinterpret_cast<cx<T>*>(col_row_tables<T, NT, EPT, C>(lds) + COL_ROW_TABLES * NT);
+}
+template <typename T, int NT, int EPT, int C>
+constexpr size_t col_lds_bytes(bool xl_tab) {
+    return (size_t)lds_elems<NT, EPT, C, false>() * sizeof(cx<T>) + COL_ROW_TABLES * (size_t)NT * sizeof(T) +
+           (xl_tab ? XL_COL_TAB_ELEMS * sizeof(cx<T>) : 0);
+}
 template <typename T, int NT, int EPT, int DIR, int C, int XL, int XLT>
 __device__ __forceinline__ void col_fft(cx<T> (&x)[EPT], cx<T>* lds, const cx<T>* __restrict__ tw,
                                         const ColTw<T, NT, EPT, XLT>& ctw, int j, int c) {
     if constexpr (XL) {   // two table entries, read per transform: 8 more live registers spill the fp64 kernels
-        const XlColTw<T> t = xl_col_load_tw<T>(tw, j);
+        // (table twiddles: the second entry is the lane's column of the workgroup's stage-two table instead, filled in k_cols)
+        const XlColTw<T> t = xl_col_load_tw<T>(tw, j, col_xl_tab<T, NT, EPT, C>(lds));
         xl_col_fft512<T, DIR>(x, lds, t, (int)threadIdx.x);
     } else if constexpr (!XLT && ColTw<T, NT, EPT, XLT>::RT) {
         NoHook nohook;
@@ -234,21 +250,37 @@ __device__ __forceinline__ void col_fft(cx<T> (&x)[EPT], cx<T>* lds, const cx<T>
     }
 }
 
-// f=0: u^ = 2 pi i ky psi   f=1: v^ = -2 pi i kx psi   f=2: dx w^ = 2 pi i kx w   f=3: dy w^ = 2 pi i ky w,
-// psi = -w / lap with lap(0,0) patched to 1 (`origin`); `us` = w^ / n^2
-template <typename T>
-__device__ __forceinline__ cx<T> plane_value(int f, cx<T> us, T kx, T ky, bool origin) {
-    constexpr T TWO_PI = (T)6.283185307179586476925286766559;
-    constexpr T M4PI2 = (T)(-39.478417604357434475337963999505);
+// Value of plane f at one spectral element, `u` = w^ (unscaled):
+// f=0: u^ = 2 pi i ky psi   f=1: v^ = -2 pi i kx psi   f=2: dx w^ = 2 pi i kx w   f=3: dy w^ = 2 pi i ky w,   all / n^2,
+// psi = -w / lap, lap = -4 pi^2 (kx^2 + ky^2), lap(0,0) patched to 1 (`origin`; kx = ky = 0 there, so the value is 0).
+// Everything that does not change from element to element is out of the element: 1 / n^2, 2 pi and the signs are the
+// compile-time constants P = 1 / (2 pi n^2), S = 2 pi / n^2 (PlaneConst), and the column's factor `kyc` (ky P for plane 0,
+// ky S for plane 3: plane_col_const) is formed once per thread and plane.  A plane-0/1 element costs mul + FMA, the
+// reciprocal and three or four products, a plane-2/3 element two or three (scaling every element by 1 / n^2, rebuilding lap
+// and 2 pi k per element: 12 + the reciprocal, resp. 5); the fp64 plane passes are bound by vector issue.  Nothing is
+// carried from plane to plane: the kernels sit at their 128-register cap without scratch, and one more live double spills
+// them -- for the same reason -1/lap is formed per plane (eight values across a transform; the 4 KB of LDS a tile has left
+// do not hold them).
+template <typename T, int N>
+struct PlaneConst {
+    static constexpr __host__ __device__ T P() { return (T)(0.15915494309189533576888376337251 / ((double)N * (double)N)); }
+    static constexpr __host__ __device__ T S() { return (T)(6.283185307179586476925286766559 / ((double)N * (double)N)); }
+};
+template <typename T, int N>
+__device__ __forceinline__ T plane_col_const(int f, T ky) {
+    return ky * (f == 0 ? PlaneConst<T, N>::P() : PlaneConst<T, N>::S());
+}
+template <typename T, int N>
+__device__ __forceinline__ cx<T> plane_value(int f, cx<T> u, T kx, T ky, T kyc, bool origin) {
+    T c;
     if (f < 2) {
-        T lap = M4PI2 * (kx * kx + ky * ky);
-        if (origin) lap = (T)1;
-        us = cscale(us, -fast_rcp(lap));
+        T d = fma(ky, ky, kx * kx);
+        if (origin) d = (T)1;
+        c = (f == 0 ? kyc : kx * -PlaneConst<T, N>::P()) * fast_rcp(d);
+    } else {
+        c = f == 2 ? kx * PlaneConst<T, N>::S() : kyc;
     }
-    const T kk = (f == 0 || f == 3) ? ky : kx;
-    cx<T> v = mul_i(cscale(us, TWO_PI * kk));
-    if (f == 1) v = mk<T>(-v.x, -v.y);
-    return v;
+    return mk<T>(-u.y * c, u.x * c);
 }
 
 // PACKED NYQUIST COLUMN (a.nyq).  m = n/2 + 1 columns are n/2 / C full tiles plus ONE lone column, whose tile costs a
@@ -269,18 +301,18 @@ __device__ __forceinline__ void emit_planes(const ColArgs<T>& a, const cx<T> (&u
                                             const ColTw<T, (N >> SP), EPT, XL>& ctw, bool nyq_tile, const cx<T>* un) {
     constexpr int NT = N >> SP;
     constexpr int G = NT / EPT;
-    const T inv_n2 = (T)1 / ((T)N * (T)N);
     const T ky = valid ? a.ky[jc] : (T)0;
     const bool nyq_lane = nyq_tile && c == 0;
     const T ky_n = nyq_tile ? a.ky[a.m - 1] : (T)0;
 #pragma unroll 1
     for (int f = 0; f < 4; ++f) {
         cx<T> x[EPT];
+        const T kyc = plane_col_const<T, N>(f, ky);
 #pragma unroll
         for (int t = 0; t < EPT; ++t) {
             const int sl = j + t * G;
             const int i = SP ? 2 * sl + q : sl;
-            const cx<T> v = plane_value<T>(f, cscale(u[t], inv_n2), rt_kx[sl], ky, i == 0 && jc == 0);
+            const cx<T> v = plane_value<T, N>(f, u[t], rt_kx[sl], ky, kyc, i == 0 && jc == 0);
             x[t] = valid ? v : mk<T>((T)0, (T)0);
         }
         if (nyq_tile && !(a.ablate & 64)) {   // block-uniform.  Three short phases with the WHOLE workgroup (a row per thread), so that
@@ -295,8 +327,9 @@ __device__ __forceinline__ void emit_planes(const ColArgs<T>& a, const cx<T> (&u
                 // row -i of the column: local index of the same parity
                 const int ms = (SP && q) ? NT - 1 - sl : (NT - sl) % NT;
                 const cx<T> v0 = S0[sl], m0 = S0[ms];
-                const cx<T> vn = plane_value<T>(f, cscale(un[sl], inv_n2), rt_kx[sl], ky_n, false);
-                const cx<T> mn = plane_value<T>(f, cscale(un[ms], inv_n2), rt_kx[ms], ky_n, false);
+                const T kyc_n = plane_col_const<T, N>(f, ky_n);
+                const cx<T> vn = plane_value<T, N>(f, un[sl], rt_kx[sl], ky_n, kyc_n, false);
+                const cx<T> mn = plane_value<T, N>(f, un[ms], rt_kx[ms], ky_n, kyc_n, false);
                 const cx<T> h0 = mk<T>((T)0.5 * (v0.x + m0.x), (T)0.5 * (v0.y - m0.y));
                 const cx<T> hn = mk<T>((T)0.5 * (vn.x + mn.x), (T)0.5 * (vn.y - mn.y));
                 SZ[sl] = mk<T>(h0.x - hn.y, h0.y + hn.x);   // h0 + i hn
@@ -410,7 +443,7 @@ __global__ __launch_bounds__(C*((N >> SP) / EPT), MINW) void k_cols(ColArgs<T> a
     // per-row constants (kx, separable parts of the linear term and of the mask) live in LDS behind the
     // exchange tile: every later use is an LDS read instead of a dependent global load; per-column
     // constants and the forcing column range are fetched up front, before the transform needs them
-    T* rt_kx = reinterpret_cast<T*>(lds + lds_elems<NT, EPT, C, false>());
+    T* rt_kx = col_row_tables<T, NT, EPT, C>(lds);
     T* rt_lin = rt_kx + NT;
     T* rt_mask = rt_lin + NT;
     cx<T>* un_lds = reinterpret_cast<cx<T>*>(rt_lin);   // [NT]: Nyquist-column state (a.nyq), overlays rt_lin + rt_mask
@@ -420,6 +453,9 @@ __global__ __launch_bounds__(C*((N >> SP) / EPT), MINW) void k_cols(ColArgs<T> a
     // Called AFTER the tile's own loads have been issued: the table reads (three loads whose results go to LDS, in a
     // loop the compiler does not move loads across) then ride in the shadow of the tile's memory round trip instead
     // of adding two of their own in front of it.  The null tables of a non-separable plan are read through `kx`.
+    // (XL_TAB instantiations of the transforming modes: the barrier that makes the tables visible stands in FRONT of the
+    // first transform, which twiddles from LDS before its own first barrier -- there the table reads are waited for with
+    // the tile's loads instead of behind the transform.)
     auto stage_tables = [&]() {
         if constexpr (NEEDS_TABLES) {
             const T* lin_r = a.sep ? a.lin_r : a.kx;
@@ -441,6 +477,10 @@ __global__ __launch_bounds__(C*((N >> SP) / EPT), MINW) void k_cols(ColArgs<T> a
 
     ColTw<T, NT, EPT, XL> ctw;
     ctw.load(a.tw, j);
+    // cross-lane tiles with table twiddles: the 8 x 8 roots of the second stage, behind the row tables; its read goes out ahead
+    // of the tile's own, and the first barrier below makes it visible
+    constexpr bool XL_TAB = XL && xl_col_direct<T>();
+    if constexpr (XL_TAB) xl_col_fill_tab<T>(col_xl_tab<T, NT, EPT, C>(lds), a.tw, (int)threadIdx.x);
     cx<T> x[EPT];
     if constexpr (MODE == MODE_A) {
         {
@@ -471,8 +511,9 @@ __global__ __launch_bounds__(C*((N >> SP) / EPT), MINW) void k_cols(ColArgs<T> a
         for (int t = 0; t < EPT; ++t)
             x[t] = col_live ? TCFD_COL_LD(a.in + inbase + (wq + (size_t)(jin + t * G)) * in_ld) : mk<T>((T)0, (T)0);
         stage_tables();
+        if constexpr (XL_TAB) __syncthreads();   // this transform twiddles from the table before its first barrier; row tables visible too
         if (!(a.ablate & 1) && tile_live) col_fft<T, NT, EPT, DIR, C, XLF ? 1 : 0, XL>(x, lds, a.tw, ctw, j, c);
-        if constexpr (NEEDS_TABLES) __syncthreads();  // row tables visible (a one-pass transform has no barrier)
+        if constexpr (NEEDS_TABLES && !XL_TAB) __syncthreads();  // row tables visible (a one-pass transform has no barrier)
 
         if constexpr (MODE == MODE_FWD || MODE == MODE_INV) {
             if (valid) {
@@ -1695,7 +1736,7 @@ static int launch_cols_v(const tcfd_ns2d_plan* p, ColArgs<T> a, long batch, hipS
     constexpr int NT = N >> SP;
     constexpr int G = NT / EPT;
     // + TCFD_COLS_LDS_PAD bytes: an experiment knob that caps the workgroups a CU takes (occupancy A/B without a rebuild)
-    const size_t lds = (size_t)lds_elems<NT, EPT, C, false>() * sizeof(cx<T>) + 3 * (size_t)NT * sizeof(T) + (size_t)p->tune.cols_lds_pad;
+    size_t lds = col_lds_bytes<T, NT, EPT, C>(false) + (size_t)p->tune.cols_lds_pad;
     a.m = p->m;
     a.ldw = p->ldw;
     a.ntiles = (p->m + C - 1) / C;
@@ -1745,6 +1786,7 @@ static int launch_cols_v(const tcfd_ns2d_plan* p, ColArgs<T> a, long batch, hipS
     constexpr bool XL_OK = (NT == 512 && EPT == 8 && C == 8 && MODE != MODE_FWD && MODE != MODE_INV);
     if constexpr (XL_OK) {
         if (p->tune.cols_xl) {
+            lds = col_lds_bytes<T, NT, EPT, C>(xl_col_direct<T>()) + (size_t)p->tune.cols_lds_pad;   // + the stage-two roots
             a.nt_planes = p->tune.nt_planes > 0;
             static DevOnce once_x, once_xn;
             if constexpr (NYQ_MODE) {
