@@ -82,8 +82,6 @@ typedef struct tcfd_fvm_plan tcfd_fvm_plan;
 
 #define TCFD_ABI_VERSION 13  /* what tcfd_version() of a library built from THIS header returns */
 
-#ifndef TCFD_H_TYPES_ONLY   /* (the library's second compilation unit wants the types without the prototypes) */
-
 const char* tcfd_last_error(void);
 /* ABI revision of the library that was loaded.  It changes whenever an entry point changes its argument list or the
  * meaning of an argument (round 3 turned the float scalars of the tcfd_fno_* calls into doubles and gave tcfd_fno_contract
@@ -715,8 +713,6 @@ int tcfd_data_affine(const void* x, const void* mean, const void* std_, void* ou
                      double eps, int mode, int x_dtype, int stat_dtype, int out_dtype, void* stream);
 int tcfd_data_moments(const void* x, void* mean, void* std_, long rows, long stat_count, long inner, int x_dtype, int stat_dtype,
                       void* stream);
-
-#endif /* TCFD_H_TYPES_ONLY */
 
 #ifdef __cplusplus
 }

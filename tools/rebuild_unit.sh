@@ -9,8 +9,9 @@ case "$1" in
   pw)   hipcc $F -c tcfd_fno_pw.hip -o tcfd_fno_pw.o ;;
   tiles) hipcc $F -c tcfd_fno_tiles.hip -o tcfd_fno_tiles.o ;;
   loss) hipcc $F -c tcfd_loss.hip -o tcfd_loss.o ;;
-  ns2d) hipcc $F -DTCFD_UNIT=0 -c tcfd_ns2d.hip -o tcfd_ns2d.o & hipcc $F -DTCFD_UNIT=1 -c tcfd_ns2d.hip -o tcfd_ns2d_f32.o & wait ;;
+  ns2d) hipcc $F -DTCFD_REAL=double -c tcfd_ns2d_sized.hip -o tcfd_ns2d_f64.o & hipcc $F -DTCFD_REAL=float -c tcfd_ns2d_sized.hip -o tcfd_ns2d_f32.o &
+        hipcc $F -c tcfd_ns2d.hip -o tcfd_ns2d.o & hipcc $F -c tcfd_ns2d_refine.hip -o tcfd_ns2d_refine.o & wait ;;
   *) echo "unit?"; exit 2 ;;
 esac
-hipcc --offload-arch=gfx950 -shared -fPIC tcfd_ns2d.o tcfd_ns2d_f32.o tcfd_fno.o tcfd_fno_pw.o tcfd_fno_tiles.o tcfd_loss.o -o libtcfd_hip.so.tmp -Wl,-rpath,/opt/rocm/lib
+hipcc --offload-arch=gfx950 -shared -fPIC tcfd_ns2d.o tcfd_ns2d_f64.o tcfd_ns2d_f32.o tcfd_ns2d_refine.o tcfd_fno.o tcfd_fno_pw.o tcfd_fno_tiles.o tcfd_loss.o -o libtcfd_hip.so.tmp -Wl,-rpath,/opt/rocm/lib
 mv libtcfd_hip.so.tmp libtcfd_hip.so

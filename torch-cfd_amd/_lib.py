@@ -24,7 +24,7 @@ CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_NAME = "libtcfd_hip.so"
 LIB_PATH = os.path.join(CSRC, LIB_NAME)
-SOURCES = ("tcfd_ns2d.hip", "tcfd_fno.hip", "tcfd_fno_pw.hip", "tcfd_fno_tiles.hip", "tcfd_fno3d.hip", "tcfd_loss.hip", "tcfd_fvm.hip",
+SOURCES = ("tcfd_ns2d.hip", "tcfd_ns2d_sized.hip", "tcfd_ns2d_refine.hip", "tcfd_fno.hip", "tcfd_fno_pw.hip", "tcfd_fno_tiles.hip", "tcfd_fno3d.hip", "tcfd_loss.hip", "tcfd_fvm.hip",
            "tcfd_grf.hip", "tcfd_residual.hip", "tcfd_data.hip")
 
 TCFD_C64, TCFD_C128 = 0, 1
@@ -71,13 +71,17 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
         lock.close()
 
 
-# compile jobs: (source, extra flags, object).  tcfd_ns2d.hip is compiled twice -- unit 0 = C ABI + float64 kernels, unit 1 =
-# float32 kernels -- and the FNO kernels are three files (transforms + contraction / pointwise block / tiled backward; the tiled
-# backward twice: unit 0 = the SFNO's blocks, unit 1 = the FNO3d baseline's), so that
-# the hipcc processes take ~4.5 minutes side by side (3.5 before the 4096-point instantiations) instead of one after the other.  tcfd_fvm.hip (finite-volume solver) is
-# compiled twice the same way: unit 0 = C ABI + float64 kernels, unit 1 = float32 kernels.
-JOBS = (("tcfd_ns2d.hip", ("-DTCFD_UNIT=0",), "tcfd_ns2d.o"),
-        ("tcfd_ns2d.hip", ("-DTCFD_UNIT=1",), "tcfd_ns2d_f32.o"),
+# compile jobs: (source, extra flags, object).  All of them run side by side, so there are at most 16 (the CPUs a build can count
+# on).  The spectral solver is three files: its C ABI with the size-free kernels (tcfd_ns2d.hip), the size-templated kernels
+# (tcfd_ns2d_sized.hip, compiled twice: the float64 and the float32 instantiations) and the refiner (tcfd_ns2d_refine.hip).  The
+# FNO kernels are three files (transforms + contraction / pointwise block / tiled backward; the tiled backward twice: unit 0 =
+# the SFNO's blocks, unit 1 = the FNO3d baseline's), so that the hipcc processes take ~4.5 minutes side by side (3.5 before the
+# 4096-point instantiations) instead of one after the other.  tcfd_fvm.hip (finite-volume solver) is compiled twice: unit 0 =
+# C ABI + float64 kernels, unit 1 = float32 kernels.
+JOBS = (("tcfd_ns2d_sized.hip", ("-DTCFD_REAL=double",), "tcfd_ns2d_f64.o"),
+        ("tcfd_ns2d_sized.hip", ("-DTCFD_REAL=float",), "tcfd_ns2d_f32.o"),
+        ("tcfd_ns2d.hip", (), "tcfd_ns2d.o"),
+        ("tcfd_ns2d_refine.hip", (), "tcfd_ns2d_refine.o"),
         ("tcfd_fno.hip", (), "tcfd_fno.o"),
         ("tcfd_fno_pw.hip", (), "tcfd_fno_pw.o"),
         ("tcfd_fno_tiles.hip", ("-DTCFD_TILES_UNIT=0",), "tcfd_fno_tiles.o"),

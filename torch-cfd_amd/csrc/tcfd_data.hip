@@ -30,18 +30,10 @@
 #include <cstdint>
 #include <type_traits>
 
-#include "../../include/tcfd.h"
+#include "tcfd_host.hpp"
 
 // x * s + m must round the product before the sum, as the two torch operations of the reference do
 #pragma clang fp contract(off)
-
-int tcfd_set_error(int code, const char* fmt, ...);  // defined in tcfd_ns2d.hip
-#define FAIL(...) tcfd_set_error(__VA_ARGS__)
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return FAIL(TCFD_EHIP, "%s: %s", #expr, hipGetErrorString(e_));      \
-    } while (0)
 
 namespace {
 

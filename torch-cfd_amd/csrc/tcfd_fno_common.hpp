@@ -6,16 +6,7 @@
 
 #include <cstdlib>
 
-#include "../../include/tcfd.h"
-
-extern "C" const char* tcfd_last_error(void);
-int tcfd_set_error(int code, const char* fmt, ...);  // defined in tcfd_ns2d.hip
-#define FAIL(...) tcfd_set_error(__VA_ARGS__)
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return FAIL(TCFD_EHIP, "%s: %s", #expr, hipGetErrorString(e_));      \
-    } while (0)
+#include "tcfd_host.hpp"
 
 template <typename K>
 static int set_lds_attr(K kernel, size_t bytes) {
@@ -23,11 +14,6 @@ static int set_lds_attr(K kernel, size_t bytes) {
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)bytes));
     return 0;
-}
-
-static int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e && *e ? atoi(e) : dflt;
 }
 
 // ------------------------------------------------------------------ per-launch event timing of the FNO kernels (measurement aid)

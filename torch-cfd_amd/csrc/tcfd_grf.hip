@@ -26,19 +26,11 @@
 #include <cmath>
 #include <cstdint>
 
-#include "../../include/tcfd.h"
+#include "tcfd_host.hpp"
 
 // a * b - c * d must round both products: a contracted form leaves a residue where the two are equal, and the
 // imaginary parts of the self-conjugate modes (and H(-k) = conj H(k) on the column ky = 0) are exact only without it
 #pragma clang fp contract(off)
-
-int tcfd_set_error(int code, const char* fmt, ...);  // defined in tcfd_ns2d.hip
-#define FAIL(...) tcfd_set_error(__VA_ARGS__)
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return FAIL(TCFD_EHIP, "%s: %s", #expr, hipGetErrorString(e_));      \
-    } while (0)
 
 namespace {
 

@@ -25,21 +25,11 @@
 #include <cstring>
 #include <vector>
 
-#include "../../include/tcfd.h"
+#include "tcfd_host.hpp"
 #include "tcfd_fft.hpp"
 #include "tcfd_loss_plan.hpp"
 
 using namespace tcfd;
-
-extern "C" const char* tcfd_last_error(void);
-int tcfd_set_error(int code, const char* fmt, ...);  // defined in tcfd_ns2d.hip
-#define FAIL(...) tcfd_set_error(__VA_ARGS__)
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return FAIL(TCFD_EHIP, "%s: %s", #expr, hipGetErrorString(e_));      \
-    } while (0)
-
 
 typedef unsigned int b128 __attribute__((ext_vector_type(4)));
 

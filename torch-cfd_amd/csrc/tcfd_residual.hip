@@ -37,20 +37,11 @@
 #include <cstdint>
 #include <cstdio>
 
-#include "../../include/tcfd.h"
+#include "tcfd_host.hpp"
 #include "tcfd_fft.hpp"
 #include "tcfd_loss_plan.hpp"
 
 using namespace tcfd;
-
-extern "C" const char* tcfd_last_error(void);
-int tcfd_set_error(int code, const char* fmt, ...);  // defined in tcfd_ns2d.hip
-#define FAIL(...) tcfd_set_error(__VA_ARGS__)
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return FAIL(TCFD_EHIP, "%s: %s", #expr, hipGetErrorString(e_));      \
-    } while (0)
 
 // elements per lane of the row transforms (one transform inside one wave) and of the column tiles: the loss kernels' choice
 template <typename T, int N>
