@@ -46,9 +46,19 @@ def _hipcc() -> str:
     return "hipcc"
 
 
-def build_library(force: bool = False, verbose: bool = False) -> str:
+def build_library(force: bool = False, verbose: bool = False, only=None) -> str:
     """Compile csrc/*.hip for gfx950 into csrc/libtcfd_hip.so (cross-compiles
-    without a GPU).  Rebuilds only when a source/header is newer than the .so."""
+    without a GPU).  Rebuilds only when a source/header is newer than the .so.
+
+    ``only``: an iterable of source names (``"tcfd_fno_pw.hip"``).  Only their jobs are compiled, the objects of the other
+    jobs are taken as a full build left them, and the library is linked anew from all of them.  The caller vouches that no
+    other source depends on what changed (a header, say)."""
+    if only is not None:
+        only = tuple(only)
+        unknown = sorted(set(only) - {src for src, _, _ in JOBS})
+        if unknown:
+            raise TcfdError("build_library(only=...): no compile job for %s (sources: %s)" % (", ".join(unknown), ", ".join(SOURCES)))
+    force = force or only is not None
     srcs = [os.path.join(CSRC, s) for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
     deps = srcs + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
     deps.append(os.path.join(INCLUDE, "tcfd.h"))
@@ -65,48 +75,50 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     try:
         if not force and fresh():
             return LIB_PATH
-        return _build_locked(srcs, verbose)
+        return _build_locked(verbose, only)
     finally:
         fcntl.flock(lock, fcntl.LOCK_UN)
         lock.close()
 
 
 # compile jobs: (source, extra flags, object).  All of them run side by side, so there are at most 16 (the CPUs a build can count
-# on).  The spectral solver is three files: its C ABI with the size-free kernels (tcfd_ns2d.hip), the size-templated kernels
-# (tcfd_ns2d_sized.hip, compiled twice: the float64 and the float32 instantiations) and the refiner (tcfd_ns2d_refine.hip).  The
-# FNO kernels are three files (transforms + contraction / pointwise block / tiled backward; the tiled backward twice: unit 0 =
-# the SFNO's blocks, unit 1 = the FNO3d baseline's), so that the hipcc processes take ~4.5 minutes side by side (3.5 before the
-# 4096-point instantiations) instead of one after the other.  tcfd_fvm.hip (finite-volume solver) is compiled twice: unit 0 =
-# C ABI + float64 kernels, unit 1 = float32 kernels.
+# on), and the build takes at least as long as its slowest job.  The rule: one compile per source; a source is compiled more than once
+# only where one compile would lengthen the whole build.  Today that is tcfd_ns2d_sized.hip alone: the size-templated kernels of
+# the spectral solver, once per precision, each about as long as tcfd_fno_pw.hip, the build's other bound (one unit with both
+# precisions took 7 minutes of hipcc 7 at -O3, against ~4.5 for each of the three on 8 cores).  Next to them, each alone:
+# tcfd_fno_tiles.hip 62 s, tcfd_residual.hip about a minute, tcfd_fvm.hip 4 s -- nowhere near that path, so nothing is gained by
+# splitting them.  build_library(force=True) on an 8-core machine, the 16 jobs of the earlier two-unit split of those three
+# against these 13, two runs each in turn: 189.5 s, 226.1 s (13), 224.4 s, 209.0 s (13) -- the same within the 35 s the 16-job
+# build differs from itself.
 JOBS = (("tcfd_ns2d_sized.hip", ("-DTCFD_REAL=double",), "tcfd_ns2d_f64.o"),
         ("tcfd_ns2d_sized.hip", ("-DTCFD_REAL=float",), "tcfd_ns2d_f32.o"),
         ("tcfd_ns2d.hip", (), "tcfd_ns2d.o"),
         ("tcfd_ns2d_refine.hip", (), "tcfd_ns2d_refine.o"),
         ("tcfd_fno.hip", (), "tcfd_fno.o"),
         ("tcfd_fno_pw.hip", (), "tcfd_fno_pw.o"),
-        ("tcfd_fno_tiles.hip", ("-DTCFD_TILES_UNIT=0",), "tcfd_fno_tiles.o"),
-        ("tcfd_fno_tiles.hip", ("-DTCFD_TILES_UNIT=1",), "tcfd_fno_tiles_fno3d.o"),
+        ("tcfd_fno_tiles.hip", (), "tcfd_fno_tiles.o"),
         ("tcfd_fno3d.hip", (), "tcfd_fno3d.o"),
         ("tcfd_loss.hip", (), "tcfd_loss.o"),
-        ("tcfd_fvm.hip", ("-DTCFD_UNIT=0",), "tcfd_fvm.o"),
-        ("tcfd_fvm.hip", ("-DTCFD_UNIT=1",), "tcfd_fvm_f32.o"),
+        ("tcfd_fvm.hip", (), "tcfd_fvm.o"),
         ("tcfd_grf.hip", (), "tcfd_grf.o"),
-        # the residual loss, twice as well: unit 0 = C ABI + float64 kernels + the small losses, unit 1 = float32 kernels
-        ("tcfd_residual.hip", ("-DTCFD_RES_UNIT=0",), "tcfd_residual.o"),
-        ("tcfd_residual.hip", ("-DTCFD_RES_UNIT=1",), "tcfd_residual_f32.o"),
+        ("tcfd_residual.hip", (), "tcfd_residual.o"),
         ("tcfd_data.hip", (), "tcfd_data.o"))
 
 
-def _build_locked(srcs, verbose):
-    objs = []
+def _build_locked(verbose, only=None):
+    jobs = [job for job in JOBS if only is None or job[0] in only]
+    objs = [os.path.join(CSRC, obj) for _, _, obj in JOBS]   # the link takes every object, rebuilt or not
+    missing = [obj for job, obj in zip(JOBS, objs) if job not in jobs and not os.path.exists(obj)]
+    if missing:
+        raise TcfdError("build_library(only=...): %s missing and not among the sources asked for: run the full build"
+                        % ", ".join(os.path.basename(m) for m in missing))
     procs = []
-    for src, flags, obj in JOBS:
+    for src, flags, obj in jobs:
         s, o = os.path.join(CSRC, src), os.path.join(CSRC, obj)
         cmd = [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", *flags, "-c", s, "-o", o]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
-        objs.append(o)
     for cmd, p in procs:
         out, _ = p.communicate()
         if p.returncode != 0:
@@ -287,3 +299,7 @@ def dptr_of_tensor(t: "torch.Tensor"):
 
 def current_stream_ptr(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
+
+
+if __name__ == "__main__":   # python -m torch_cfd_amd._lib [SOURCE.hip ...]: the full build, or those sources' objects and the link
+    print(build_library(force=True, verbose=True, only=sys.argv[1:] or None))

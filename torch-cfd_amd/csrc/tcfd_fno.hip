@@ -150,16 +150,15 @@ extern "C" int tcfd_fno_plan_create_dtype(tcfd_fno_plan** out, int X, int Y, int
     return 0;
 }
 
-static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 __host__ __device__ constexpr size_t al16c(size_t x) { return (x + 15) & ~(size_t)15; }
 
 extern "C" size_t tcfd_fno_workspace_bytes(const tcfd_fno_plan* p, int batch, int cin, int cout) {
     if (!p) return 0;
     const size_t Q = (size_t)2 * p->my * p->mt;
     const int cmax = std::max(cin, cout);
-    const size_t w = al256((size_t)batch * cmax * p->X * Q * csize(p));        // W1 / W2 (shared)
-    const size_t v = al256((size_t)batch * cin * 2 * p->mx * Q * csize(p));    // truncated input spectrum
-    const size_t o = al256((size_t)batch * cout * 2 * p->mx * Q * csize(p));   // truncated output spectrum
+    const size_t w = align256((size_t)batch * cmax * p->X * Q * csize(p));        // W1 / W2 (shared)
+    const size_t v = align256((size_t)batch * cin * 2 * p->mx * Q * csize(p));    // truncated input spectrum
+    const size_t o = align256((size_t)batch * cout * 2 * p->mx * Q * csize(p));   // truncated output spectrum
     return w + v + o;
 }
 
@@ -1310,8 +1309,8 @@ static int spectral_conv_impl(const tcfd_fno_plan* p, const void* v, const void*
     const int cmax = std::max(cin, cout);
     unsigned char* base = (unsigned char*)ws;
     ct* W = (ct*)base;
-    ct* V = (ct*)(base + al256((size_t)batch * cmax * p->X * Q * sizeof(ct)));
-    ct* O = (ct*)((unsigned char*)V + al256((size_t)batch * cin * 2 * p->mx * Q * sizeof(ct)));
+    ct* V = (ct*)(base + align256((size_t)batch * cmax * p->X * Q * sizeof(ct)));
+    ct* O = (ct*)((unsigned char*)V + align256((size_t)batch * cin * 2 * p->mx * Q * sizeof(ct)));
     int rc;
     if ((rc = do_fwd_ty<T>(p, (const T*)v, W, (long)batch * cin * p->X, (T)fwd_scale, st))) return rc;
     if ((rc = do_fwd_x<T>(p, W, V, (long)batch * cin, st))) return rc;

@@ -19,7 +19,7 @@
 //     registers, the E hidden units one after the other (E is a trip count), ONE accumulator: 2 E (W + 1) flop + E GELUs per point
 //     on 4 (W + 1) bytes, ~64 flop/B at W = 10 -- bound by the vector unit (packed multiply-adds + the 10-instruction packed GELU of
 //     tcfd_fno_pw.hpp), not by memory.  The (b, E, P) hidden tensor never exists.  Its backward is the tiled matrix-pipe kernel
-//     (tcfd_fno_tiles.hip, unit 1).  With the identity between the two layers the head folds into ONE W -> 1 reduction on the host
+//     (tcfd_fno_tiles.hip).  With the identity between the two layers the head folds into ONE W -> 1 reduction on the host
 //     (fno.py) and needs no kernel of its own.
 //
 // Alignment rules of the family: 16-byte (8-byte) accesses when P % 4 (P % 2) == 0 and the base pointers are aligned, else one

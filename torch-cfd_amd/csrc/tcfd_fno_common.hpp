@@ -16,6 +16,15 @@ static int set_lds_attr(K kernel, size_t bytes) {
     return 0;
 }
 
+// compute units of the current device (the size of a persistent grid), and that device's index where the caller needs it
+static inline hipError_t current_cu_count(int* cus, int* dev_out = nullptr) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (dev_out) *dev_out = dev;
+    return e;
+}
+
 // ------------------------------------------------------------------ per-launch event timing of the FNO kernels (measurement aid)
 // Between tcfd_fno_profile_begin and tcfd_fno_profile_end every kernel launched through a FnoProfScope is bracketed by a pair of
 // HIP events on ITS launch stream (the solver's tcfd_ns2d_profile_begin / _end, process-wide here: the pointwise entry points

@@ -589,10 +589,9 @@ static int launch_pw_bwd(PwBwdArgs a, int batch, int max_waves, int* dims, hipSt
     int rc = set_lds_attr(kern, lds);
     if (rc) return rc;
     // persistent grid: exactly the resident workgroups (a second, partial round would double the run time)
-    int per_cu = 0, dev = 0, cus = 256;
+    int per_cu = 0, cus = 256;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 64 * Gm::WAVES, lds));
-    HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    HIP_TRY(current_cu_count(&cus));
     long resident = (long)std::max(per_cu, 1) * cus;
     int blocks = (int)std::min<long>({(a.total_chunks + Gm::WAVES - 1) / Gm::WAVES, (long)(max_waves / Gm::WAVES), resident});
     if (blocks < 1) blocks = 1;

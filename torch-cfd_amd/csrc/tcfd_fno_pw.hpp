@@ -256,14 +256,11 @@ __device__ __forceinline__ void pw_skip_conv(const PwArgs& a, const vf (&sv)[CI]
 #define PW_LOAD(p_) (*(p_))
 #endif
 
-// tcfd_fno_tiles.hip: the tiled all-MFMA backward (two-layer form, P % 4 == 0).  Returns 0 and sets *handled = 1 when it took the
-// call (or answered the layout query), leaves *handled = 0 for combinations it does not cover.
+// tcfd_fno_tiles.hip: the tiled all-MFMA backward (two-layer form, P % 4 == 0) of the SFNO's blocks and of the FNO3d baseline's
+// (layer tail W -> W -> W, head W -> E -> 1).  Returns 0 and sets *handled = 1 when it took the call (or answered the layout
+// query), leaves *handled = 0 for combinations it does not cover.
 int tcfd_pwb_tiles_dispatch(const PwBwdArgs& a, int batch, int ci, int cm, int co, int max_rows, int* dims, hipStream_t st,
                             int* handled);
-// tcfd_fno_tiles.hip, compile unit 1: the same kernel for the blocks of the FNO3d baseline (layer tail W -> W -> W, head W -> E -> 1);
-// tcfd_pwb_tiles_dispatch ends in it
-int tcfd_pwb_tiles_dispatch_fno3d(const PwBwdArgs& a, int batch, int ci, int cm, int co, int max_rows, int* dims, hipStream_t st,
-                                  int* handled);
 // tcfd_fno_tiles.hip: the forward block of the wide layers on the matrix pipe (same contract: *handled = 0 -> not covered)
 int tcfd_pwf_tiles_dispatch(const PwArgs& a, int batch, int ci, int cm, int co, hipStream_t st, int* handled);
 // tcfd_fno3d.hip: the rectangular members of the family (FNO3d baseline) -- forward of the single layer ci -> W and of the head

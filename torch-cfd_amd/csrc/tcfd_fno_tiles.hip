@@ -30,6 +30,10 @@
 // 16: 88, 20: 119 + 77 small ones (TilesGeom::REM4: the products whose N or M side is the 4-channel tile as 4 x 4 x 1 blocks), 24: 244, 32: 352.  A partly filled channel tile deals its channels to the rows 4q + r with r < ceil(n / 4)
 // (slot -> channel map `Ch::chan`), so the k-steps that would multiply padding are never issued.
 // Weight fragments: groups of four consecutive k-steps interleaved per lane, one ds_read_b128 at an immediate offset per group.
+//
+// One translation unit holds the kernel's three sets of instantiations, each behind a dispatch function at the end of the file:
+// the SFNO's blocks (tcfd_pwb_tiles_dispatch), the FNO3d baseline's layer tail and head (tcfd_pwb_tiles_dispatch_fno3d, internal:
+// the former ends in it) and the forward block of the wide layers on the same tiles (k_pwf_tiles, tcfd_pwf_tiles_dispatch).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -710,13 +714,12 @@ int launch_tiles(PwBwdArgs a, int batch, int max_rows, int* dims, hipStream_t st
     auto kern = k_pwb_tiles<CI, CM, CO, MODE, ACT, WPS>;
     static int lds_set_dev[64] = {0};
     int dev = 0, cus = 256, per_cu = 0;
-    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(current_cu_count(&cus, &dev));
     if (dev < 0 || dev >= 64 || !lds_set_dev[dev]) {
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)Gm::lds_of(MODE)));
         if (dev >= 0 && dev < 64) lds_set_dev[dev] = 1;
     }
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 256, Gm::lds_of(MODE)));
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     const long groups = ((a.P + 15) / 16) * batch;
     if (groups >= (1L << 30)) return FAIL(TCFD_EINVAL, "fno_pointwise_bwd: %ld groups of 16 points exceed the kernel's index range", groups);
     if ((size_t)(CI > CO ? CI : CO) * (size_t)a.P * 4 >= ((size_t)1 << 32))
@@ -749,8 +752,8 @@ int launch_tiles_mode(const PwBwdArgs& a, int batch, int max_rows, int* dims, hi
     *handled = 1;
     dims[0] = Lay::COP; dims[1] = Lay::CB; dims[2] = Lay::CM1; dims[3] = Lay::CIP; dims[4] = Lay::TOTAL; dims[5] = 0;
     if (!a.x) {                                               // layout query: dims[5] = rows a launch that fills the device writes
-        int dev = 0, cus = 256, per_cu = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) {
+        int cus = 256, per_cu = 0;
+        if (current_cu_count(&cus) == hipSuccess) {
             auto kern = k_pwb_tiles<CI, CM, CO, (MODES & 2) ? 1 : 0, (MODES & 2) ? 1 : -1, WPS>;   // (every MODE / ACT variant of a width has the same WPS and LDS)
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TilesGeom<CI, CM, CO>::LDS);
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 256, TilesGeom<CI, CM, CO>::LDS) == hipSuccess)
@@ -1022,11 +1025,10 @@ int launch_fwd_tiles(const PwArgs& a, int batch, hipStream_t st) {
     FnoProfScope prof(FNO_K_POINTWISE, st);
     using Gm = TilesFwdGeom<CI, CM, CO>;
     auto kern = k_pwf_tiles<CI, CM, CO, MODE, ACT, WPS>;
-    int dev = 0, cus = 256, per_cu = 0;
-    HIP_TRY(hipGetDevice(&dev));
+    int cus = 256, per_cu = 0;
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)Gm::LDS));
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 256, Gm::LDS));
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    HIP_TRY(current_cu_count(&cus));
     const long groups = ((a.P + 15) / 16) * batch;
     long blocks = std::min<long>((groups + 3) / 4, (long)std::max(per_cu, 1) * cus);
     if (blocks < 1) blocks = 1;
@@ -1049,26 +1051,6 @@ int launch_fwd_tiles_mode(const PwArgs& a, int batch, hipStream_t st) {
 
 }  // namespace
 
-#if !defined(TCFD_TILES_UNIT) || TCFD_TILES_UNIT != 1
-// The widths the reference's own code uses (10: fno/train.py:293; 16: fno/sfno_pytest.py:261; 20: its notebooks) and the
-// even widths around them (4 ... 16, 24, 32), with its channel expansion of 4 (fno/sfno.py:479).  The kernel needs the block's saved output /
-// pre-activation unless the output activation is the identity.
-int tcfd_pwb_tiles_dispatch(const PwBwdArgs& a, int batch, int ci, int cm, int co, int max_rows, int* dims, hipStream_t st,
-                            int* handled) {
-    *handled = 0;
-    if (a.pe || a.per_sample || a.P % 4 != 0) return 0;                                      // (known at the layout query too)
-    if (a.x && (max_rows < 4 || !a.w1 || (a.act2 != 0 && !a.out))) return 0;
-#define PWT_CASE(CI_, CM_, CO_, WPS_)                                                          \
-    if (ci == CI_ && cm == CM_ && co == CO_)                                                    \
-        return launch_tiles_mode<CI_, CM_, CO_, WPS_>(a, batch, max_rows, dims, st, handled);
-    PWT_CASE(4, 16, 4, 2) PWT_CASE(6, 24, 6, 2) PWT_CASE(8, 32, 8, 2) PWT_CASE(10, 40, 10, 2) PWT_CASE(12, 48, 12, 2)
-    PWT_CASE(14, 56, 14, 2) PWT_CASE(16, 64, 16, 2) PWT_CASE(20, 80, 20, 1) PWT_CASE(24, 96, 24, 1) PWT_CASE(32, 128, 32, 1)
-#undef PWT_CASE
-    return tcfd_pwb_tiles_dispatch_fno3d(a, batch, ci, cm, co, max_rows, dims, st, handled);
-}
-#endif   // TCFD_TILES_UNIT != 1
-
-#if !defined(TCFD_TILES_UNIT) || TCFD_TILES_UNIT == 1
 // The blocks of the FNO3d baseline (fno/fno3d.py:119-236) on the same kernel -- every channel dimension is tiled, nothing in it ties
 // the hidden width to 4 x the width:
 //   * the layer tail  act(mlp2(GELU(mlp1(K v))) + w(v)):  W -> W -> W with the skip convolution (or none), every even width 4 ... 32;
@@ -1077,9 +1059,9 @@ int tcfd_pwb_tiles_dispatch(const PwBwdArgs& a, int batch, int ci, int cm, int c
 //     have co on a side (dh, dW2: 8 + 32 of the 128 matrix instructions per 16 points at W = 10, E = 128); the E erf-GELUs with their
 //     derivatives take about as long as all the products and do not overlap them (profiles/r03_mfma_f32_vs_valu_overlap.txt), so
 //     the kernel is bound by instruction issue, ~10 x above its HBM time.
-// A compile unit of its own (TCFD_TILES_UNIT=1): these instances would double the build time of the SFNO's.
-int tcfd_pwb_tiles_dispatch_fno3d(const PwBwdArgs& a, int batch, int ci, int cm, int co, int max_rows, int* dims, hipStream_t st,
-                                  int* handled) {
+// Internal to this file: tcfd_pwb_tiles_dispatch below ends in it.
+static int tcfd_pwb_tiles_dispatch_fno3d(const PwBwdArgs& a, int batch, int ci, int cm, int co, int max_rows, int* dims,
+                                         hipStream_t st, int* handled) {
     *handled = 0;
 #define PWT_TAIL(W_, WPS_)                                                                     \
     if (ci == W_ && cm == W_ && co == W_)                                                       \
@@ -1097,9 +1079,24 @@ int tcfd_pwb_tiles_dispatch_fno3d(const PwBwdArgs& a, int batch, int ci, int cm,
 #undef PWT_HEAD
     return 0;
 }
-#endif
 
-#if !defined(TCFD_TILES_UNIT) || TCFD_TILES_UNIT != 1
+// The widths the reference's own code uses (10: fno/train.py:293; 16: fno/sfno_pytest.py:261; 20: its notebooks) and the
+// even widths around them (4 ... 16, 24, 32), with its channel expansion of 4 (fno/sfno.py:479).  The kernel needs the block's saved output /
+// pre-activation unless the output activation is the identity.
+int tcfd_pwb_tiles_dispatch(const PwBwdArgs& a, int batch, int ci, int cm, int co, int max_rows, int* dims, hipStream_t st,
+                            int* handled) {
+    *handled = 0;
+    if (a.pe || a.per_sample || a.P % 4 != 0) return 0;                                      // (known at the layout query too)
+    if (a.x && (max_rows < 4 || !a.w1 || (a.act2 != 0 && !a.out))) return 0;
+#define PWT_CASE(CI_, CM_, CO_, WPS_)                                                          \
+    if (ci == CI_ && cm == CM_ && co == CO_)                                                    \
+        return launch_tiles_mode<CI_, CM_, CO_, WPS_>(a, batch, max_rows, dims, st, handled);
+    PWT_CASE(4, 16, 4, 2) PWT_CASE(6, 24, 6, 2) PWT_CASE(8, 32, 8, 2) PWT_CASE(10, 40, 10, 2) PWT_CASE(12, 48, 12, 2)
+    PWT_CASE(14, 56, 14, 2) PWT_CASE(16, 64, 16, 2) PWT_CASE(20, 80, 20, 1) PWT_CASE(24, 96, 24, 1) PWT_CASE(32, 128, 32, 1)
+#undef PWT_CASE
+    return tcfd_pwb_tiles_dispatch_fno3d(a, batch, ci, cm, co, max_rows, dims, st, handled);
+}
+
 // Forward block of the wide layers on the matrix pipe (k_pwf_tiles): widths 24 / 32 with cm = 4 ci, shared weights, P % 4 == 0,
 // the (batch, C, P) layout.  Measured at the config-5 grid, per launch (profiles/r05_pw_fwd_tiles_timing.json): width 24 2.61 ms
 // against 3.19 for k_pointwise, width 32 3.75 against 6.60 -- and width 16 1.76 against 1.45, width 20 2.13 against 1.66 (36 / 75
@@ -1122,4 +1119,3 @@ int tcfd_pwf_tiles_dispatch(const PwArgs& a, int batch, int ci, int cm, int co, 
 #undef PWF_CASE
     return 0;
 }
-#endif

@@ -5,7 +5,7 @@
 // Data layout: ux[b][i][j] sits at the x-face (i + 1, j + 1/2) of cell (i, j), uy[b][i][j] at the y-face (i + 1/2, j + 1);
 // q (pressure increment) and the divergence at the cell centres.  Periodic in both axes, square n x n.
 //
-// Launch sequence of one RK stage i (TCFD_UNIT 0 = fp64, 1 = fp32 instantiations):
+// Launch sequence of one RK stage i (every kernel instantiated for fp64 and fp32, chosen by the plan's dtype):
 //   k_fvm_apply    u_i = u*_i - grad q_i (forward differences of q; skipped for stage 0, whose state is u0)
 //   k_fvm_stage    k_i = explicit_terms(u_i) in registers; u*_m (+)= c_mi k_i for every later stage m and the final sum
 //                  (one instantiation per advection scheme of the plan, chosen by a host-side switch at launch)
@@ -567,14 +567,6 @@ __global__ void __launch_bounds__(256) k_fvm_apply_adj(const T* gx, const T* gy,
 
 }  // namespace
 
-#if TCFD_UNIT == 1
-using Real = float;
-#define FVM_SUFFIX f32
-#else
-using Real = double;
-#define FVM_SUFFIX f64
-#endif
-
 struct tcfd_fvm_plan {
     int n;
     int dtype;                 // TCFD_C128: fp64 fields, TCFD_C64: fp32
@@ -587,42 +579,42 @@ struct tcfd_fvm_plan {
     int scheme;                // TCFD_FVM_*: the instantiation of k_fvm_stage / k_fvm_stage_vjp, read at every launch
 };
 
-// ---- per-precision launchers (one compilation unit each); the C ABI (unit 0) dispatches on the plan's dtype
-#define CAT2(a, b) a##b
-#define CAT(a, b) CAT2(a, b)
-#define FVMFN(name) CAT(name##_, FVM_SUFFIX)
+namespace {
 
-static dim3 cell_grid(int n, long batch) { return dim3((unsigned)((n + 63) / 64), (unsigned)((n + 3) / 4), (unsigned)batch); }
-static const dim3 kCellBlock(64, 4, 1);
+// ---- launchers, templates on the field type T; the C ABI dispatches on the plan's dtype
+dim3 cell_grid(int n, long batch) { return dim3((unsigned)((n + 63) / 64), (unsigned)((n + 3) / 4), (unsigned)batch); }
+const dim3 kCellBlock(64, 4, 1);
 
-static StageConst<Real> stage_const(const tcfd_fvm_plan* p, double dt) {
-    StageConst<Real> s;
+template <typename T>
+StageConst<T> stage_const(const tcfd_fvm_plan* p, double dt) {
+    StageConst<T> s;
     const double inv_h2 = 1.0 / (p->h * p->h);
-    s.cfl = (Real)(dt / p->h);
-    s.inv_h2 = (Real)inv_h2;
-    s.sum_s = (Real)(inv_h2 + inv_h2);
-    s.nu = (Real)p->nu;
-    s.neg_drag = (Real)(-p->drag);
-    s.h = (Real)p->h;
+    s.cfl = (T)(dt / p->h);
+    s.inv_h2 = (T)inv_h2;
+    s.sum_s = (T)(inv_h2 + inv_h2);
+    s.nu = (T)p->nu;
+    s.neg_drag = (T)(-p->drag);
+    s.h = (T)p->h;
     s.drag_on = p->drag > 0.0;
     return s;
 }
 
-int FVMFN(fvm_stage_launch)(const tcfd_fvm_plan* p, const void* ux, const void* uy, const void* u0x, const void* u0y, void* kx,
-                            void* ky, void* const* tx, void* const* ty, const double* c, const int* mode, int count, long batch,
-                            double dt, hipStream_t st) {
-    Targets<Real> tg;
+template <typename T>
+int stage_launch(const tcfd_fvm_plan* p, const void* ux, const void* uy, const void* u0x, const void* u0y, void* kx, void* ky,
+                 void* const* tx, void* const* ty, const double* c, const int* mode, int count, long batch, double dt,
+                 hipStream_t st) {
+    Targets<T> tg;
     tg.count = count;
     for (int t = 0; t < MAXT; ++t) {
-        tg.x[t] = t < count ? (Real*)tx[t] : nullptr;
-        tg.y[t] = t < count ? (Real*)ty[t] : nullptr;
-        tg.c[t] = t < count ? (Real)c[t] : Real(0);
+        tg.x[t] = t < count ? (T*)tx[t] : nullptr;
+        tg.y[t] = t < count ? (T*)ty[t] : nullptr;
+        tg.c[t] = t < count ? (T)c[t] : T(0);
         tg.mode[t] = t < count ? mode[t] : 0;
     }
 #define STAGE(SCHEME)                                                                                                      \
-    hipLaunchKernelGGL((k_fvm_stage<SCHEME, Real>), cell_grid(p->n, batch), kCellBlock, 0, st, (const Real*)ux,            \
-                       (const Real*)uy, (const Real*)u0x, (const Real*)u0y, (const Real*)p->fx, (const Real*)p->fy,        \
-                       (Real*)kx, (Real*)ky, tg, stage_const(p, dt), p->n)
+    hipLaunchKernelGGL((k_fvm_stage<SCHEME, T>), cell_grid(p->n, batch), kCellBlock, 0, st, (const T*)ux, (const T*)uy,    \
+                       (const T*)u0x, (const T*)u0y, (const T*)p->fx, (const T*)p->fy, (T*)kx, (T*)ky, tg,                 \
+                       stage_const<T>(p, dt), p->n)
     switch (p->scheme) {
         case VAN_LEER: STAGE(VAN_LEER); break;
         case UPWIND: STAGE(UPWIND); break;
@@ -635,36 +627,39 @@ int FVMFN(fvm_stage_launch)(const tcfd_fvm_plan* p, const void* ux, const void* 
     return 0;
 }
 
-int FVMFN(fvm_div_launch)(const tcfd_fvm_plan* p, const void* ux, const void* uy, void* div, long batch, hipStream_t st) {
-    hipLaunchKernelGGL(k_fvm_div<Real>, cell_grid(p->n, batch), kCellBlock, 0, st, (const Real*)ux, (const Real*)uy, (Real*)div,
-                       (Real)p->h, p->n);
+template <typename T>
+int div_launch(const tcfd_fvm_plan* p, const void* ux, const void* uy, void* div, long batch, hipStream_t st) {
+    hipLaunchKernelGGL(k_fvm_div<T>, cell_grid(p->n, batch), kCellBlock, 0, st, (const T*)ux, (const T*)uy, (T*)div, (T)p->h,
+                       p->n);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-int FVMFN(fvm_mul_launch)(const tcfd_fvm_plan* p, void* spec, long batch, hipStream_t st) {
+template <typename T>
+int mul_launch(const tcfd_fvm_plan* p, void* spec, long batch, hipStream_t st) {
     const long plane = (long)p->n * (p->n / 2 + 1);
     const long total = plane * batch;
-    hipLaunchKernelGGL(k_fvm_mul<Real>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (Real*)spec, (const Real*)p->inv,
-                       plane, total);
+    hipLaunchKernelGGL(k_fvm_mul<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (T*)spec, (const T*)p->inv, plane,
+                       total);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-int FVMFN(fvm_apply_launch)(const tcfd_fvm_plan* p, const void* px, const void* py, const void* q, void* ox, void* oy, long batch,
-                            hipStream_t st) {
-    hipLaunchKernelGGL(k_fvm_apply<Real>, cell_grid(p->n, batch), kCellBlock, 0, st, (const Real*)px, (const Real*)py,
-                       (const Real*)q, (Real*)ox, (Real*)oy, (Real)p->h, p->n);
+template <typename T>
+int apply_launch(const tcfd_fvm_plan* p, const void* px, const void* py, const void* q, void* ox, void* oy, long batch,
+                 hipStream_t st) {
+    hipLaunchKernelGGL(k_fvm_apply<T>, cell_grid(p->n, batch), kCellBlock, 0, st, (const T*)px, (const T*)py, (const T*)q,
+                       (T*)ox, (T*)oy, (T)p->h, p->n);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-int FVMFN(fvm_stage_vjp_launch)(const tcfd_fvm_plan* p, const void* ux, const void* uy, const void* lx, const void* ly, void* ox,
-                                void* oy, int accumulate, long batch, double dt, hipStream_t st) {
+template <typename T>
+int stage_vjp_launch(const tcfd_fvm_plan* p, const void* ux, const void* uy, const void* lx, const void* ly, void* ox, void* oy,
+                     int accumulate, long batch, double dt, hipStream_t st) {
 #define STAGE_VJP(SCHEME)                                                                                                  \
-    hipLaunchKernelGGL((k_fvm_stage_vjp<SCHEME, Real>), cell_grid(p->n, batch), kCellBlock, 0, st, (const Real*)ux,        \
-                       (const Real*)uy, (const Real*)lx, (const Real*)ly, (Real*)ox, (Real*)oy, accumulate,                \
-                       stage_const(p, dt), p->n)
+    hipLaunchKernelGGL((k_fvm_stage_vjp<SCHEME, T>), cell_grid(p->n, batch), kCellBlock, 0, st, (const T*)ux,              \
+                       (const T*)uy, (const T*)lx, (const T*)ly, (T*)ox, (T*)oy, accumulate, stage_const<T>(p, dt), p->n)
     switch (p->scheme) {
         case VAN_LEER: STAGE_VJP(VAN_LEER); break;
         case UPWIND: STAGE_VJP(UPWIND); break;
@@ -677,61 +672,49 @@ int FVMFN(fvm_stage_vjp_launch)(const tcfd_fvm_plan* p, const void* ux, const vo
     return 0;
 }
 
-int FVMFN(fvm_apply_adj_launch)(const tcfd_fvm_plan* p, const void* gx, const void* gy, const void* q, void* const* tx,
-                                void* const* ty, const double* c, const int* mode, int count, long batch, hipStream_t st) {
-    AdjTargets<Real> tg;
+template <typename T>
+int apply_adj_launch(const tcfd_fvm_plan* p, const void* gx, const void* gy, const void* q, void* const* tx, void* const* ty,
+                     const double* c, const int* mode, int count, long batch, hipStream_t st) {
+    AdjTargets<T> tg;
     tg.count = count;
     for (int t = 0; t < MAXA; ++t) {
-        tg.x[t] = t < count ? (Real*)tx[t] : nullptr;
-        tg.y[t] = t < count ? (Real*)ty[t] : nullptr;
-        tg.c[t] = t < count ? (Real)c[t] : Real(0);
+        tg.x[t] = t < count ? (T*)tx[t] : nullptr;
+        tg.y[t] = t < count ? (T*)ty[t] : nullptr;
+        tg.c[t] = t < count ? (T)c[t] : T(0);
         tg.mode[t] = t < count ? mode[t] : 0;
     }
-    hipLaunchKernelGGL(k_fvm_apply_adj<Real>, cell_grid(p->n, batch), kCellBlock, 0, st, (const Real*)gx, (const Real*)gy,
-                       (const Real*)q, tg, (Real)p->h, p->n);
+    hipLaunchKernelGGL(k_fvm_apply_adj<T>, cell_grid(p->n, batch), kCellBlock, 0, st, (const T*)gx, (const T*)gy, (const T*)q,
+                       tg, (T)p->h, p->n);
     HIP_TRY(hipGetLastError());
     return 0;
 }
-
-#if TCFD_UNIT != 1
-// ================================================================ C ABI (unit 0)
-int fvm_stage_launch_f32(const tcfd_fvm_plan*, const void*, const void*, const void*, const void*, void*, void*, void* const*,
-                         void* const*, const double*, const int*, int, long, double, hipStream_t);
-int fvm_div_launch_f32(const tcfd_fvm_plan*, const void*, const void*, void*, long, hipStream_t);
-int fvm_mul_launch_f32(const tcfd_fvm_plan*, void*, long, hipStream_t);
-int fvm_apply_launch_f32(const tcfd_fvm_plan*, const void*, const void*, const void*, void*, void*, long, hipStream_t);
-int fvm_stage_vjp_launch_f32(const tcfd_fvm_plan*, const void*, const void*, const void*, const void*, void*, void*, int, long,
-                             double, hipStream_t);
-int fvm_apply_adj_launch_f32(const tcfd_fvm_plan*, const void*, const void*, const void*, void* const*, void* const*,
-                             const double*, const int*, int, long, hipStream_t);
-
-namespace {
 
 bool is_f64(const tcfd_fvm_plan* p) { return p->dtype == TCFD_C128; }
 size_t real_bytes(const tcfd_fvm_plan* p) { return is_f64(p) ? 8 : 4; }
 size_t field_bytes(const tcfd_fvm_plan* p, long batch) { return (size_t)batch * p->n * p->n * real_bytes(p); }
 size_t spec_bytes(const tcfd_fvm_plan* p, long batch) { return (size_t)batch * p->n * (p->n / 2 + 1) * 2 * real_bytes(p); }
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// ================================================================ C ABI
+// the launchers above, instantiated by the plan's dtype
 int stage_launch(const tcfd_fvm_plan* p, const void* ux, const void* uy, const void* u0x, const void* u0y, void* kx, void* ky,
                  void* const* tx, void* const* ty, const double* c, const int* mode, int count, long batch, double dt,
                  hipStream_t st) {
-    return is_f64(p) ? fvm_stage_launch_f64(p, ux, uy, u0x, u0y, kx, ky, tx, ty, c, mode, count, batch, dt, st)
-                     : fvm_stage_launch_f32(p, ux, uy, u0x, u0y, kx, ky, tx, ty, c, mode, count, batch, dt, st);
+    return is_f64(p) ? stage_launch<double>(p, ux, uy, u0x, u0y, kx, ky, tx, ty, c, mode, count, batch, dt, st)
+                     : stage_launch<float>(p, ux, uy, u0x, u0y, kx, ky, tx, ty, c, mode, count, batch, dt, st);
 }
 int apply_launch(const tcfd_fvm_plan* p, const void* px, const void* py, const void* q, void* ox, void* oy, long batch,
                  hipStream_t st) {
-    return is_f64(p) ? fvm_apply_launch_f64(p, px, py, q, ox, oy, batch, st) : fvm_apply_launch_f32(p, px, py, q, ox, oy, batch, st);
+    return is_f64(p) ? apply_launch<double>(p, px, py, q, ox, oy, batch, st) : apply_launch<float>(p, px, py, q, ox, oy, batch, st);
 }
 int stage_vjp_launch(const tcfd_fvm_plan* p, const void* ux, const void* uy, const void* lx, const void* ly, void* ox, void* oy,
                      int accumulate, long batch, double dt, hipStream_t st) {
-    return is_f64(p) ? fvm_stage_vjp_launch_f64(p, ux, uy, lx, ly, ox, oy, accumulate, batch, dt, st)
-                     : fvm_stage_vjp_launch_f32(p, ux, uy, lx, ly, ox, oy, accumulate, batch, dt, st);
+    return is_f64(p) ? stage_vjp_launch<double>(p, ux, uy, lx, ly, ox, oy, accumulate, batch, dt, st)
+                     : stage_vjp_launch<float>(p, ux, uy, lx, ly, ox, oy, accumulate, batch, dt, st);
 }
 int apply_adj_launch(const tcfd_fvm_plan* p, const void* gx, const void* gy, const void* q, void* const* tx, void* const* ty,
                      const double* c, const int* mode, int count, long batch, hipStream_t st) {
-    return is_f64(p) ? fvm_apply_adj_launch_f64(p, gx, gy, q, tx, ty, c, mode, count, batch, st)
-                     : fvm_apply_adj_launch_f32(p, gx, gy, q, tx, ty, c, mode, count, batch, st);
+    return is_f64(p) ? apply_adj_launch<double>(p, gx, gy, q, tx, ty, c, mode, count, batch, st)
+                     : apply_adj_launch<float>(p, gx, gy, q, tx, ty, c, mode, count, batch, st);
 }
 
 // workspace carve: [div | spectrum | q | transform scratch] for the projection, then the RK buffers of tcfd_fvm_step, or
@@ -753,7 +736,7 @@ Carve carve(const tcfd_fvm_plan* p, long batch, void* ws, int kind) {
     size_t off = 0;
     auto take = [&](size_t bytes) {
         void* r = b ? b + off : nullptr;
-        off += align_up(bytes);
+        off += align256(bytes);
         return r;
     };
     const size_t F = field_bytes(p, batch);
@@ -789,10 +772,10 @@ Carve carve(const tcfd_fvm_plan* p, long batch, void* ws, int kind) {
 
 // q of the field (px, py) into c.q
 int solve_q(const tcfd_fvm_plan* p, const void* px, const void* py, long batch, const Carve& c, hipStream_t st) {
-    int rc = is_f64(p) ? fvm_div_launch_f64(p, px, py, c.div, batch, st) : fvm_div_launch_f32(p, px, py, c.div, batch, st);
+    int rc = is_f64(p) ? div_launch<double>(p, px, py, c.div, batch, st) : div_launch<float>(p, px, py, c.div, batch, st);
     if (rc) return rc;
     if ((rc = tcfd_rfft2(p->fft, c.div, c.spec, batch, st))) return rc;
-    rc = is_f64(p) ? fvm_mul_launch_f64(p, c.spec, batch, st) : fvm_mul_launch_f32(p, c.spec, batch, st);
+    rc = is_f64(p) ? mul_launch<double>(p, c.spec, batch, st) : mul_launch<float>(p, c.spec, batch, st);
     if (rc) return rc;
     return tcfd_irfft2(p->fft, c.spec, c.q, batch, c.fftws, c.fftws_bytes, st);
 }
@@ -1067,4 +1050,3 @@ int tcfd_fvm_step_vjp(const tcfd_fvm_plan* p, const void* saved, const void* gx,
 }
 
 }  // extern "C"
-#endif

@@ -18,7 +18,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -347,7 +346,6 @@ static bool loss_n_ok(int n) {
     if (n >= 16 && n <= 1024 && (n & (n - 1)) == 0) return true;
     return n == 96 || n == 192 || n == 384 || n == 768 || n == 80 || n == 160 || n == 320 || n == 640;
 }
-static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 static int loss_ldk(const tcfd_loss_plan* p) {   // row pitch of the half-spectrum planes: n/2 + 1 rounded up to 128 bytes
     const int per_line = p->dtype == TCFD_C128 ? 8 : 16;
     return ((p->n / 2 + 1) + per_line - 1) / per_line * per_line;
@@ -394,8 +392,8 @@ extern "C" void tcfd_loss_plan_destroy(tcfd_loss_plan* p) {
 extern "C" size_t tcfd_loss_workspace_bytes(const tcfd_loss_plan* p, long batch, int nt, int nfields) {
     if (!p || batch <= 0 || nt <= 0 || nfields < 1 || nfields > 2) return 0;
     const size_t cs = p->dtype == TCFD_C128 ? 16 : 8;
-    const size_t planes = al256((size_t)nfields * batch * nt * p->n * loss_ldk(p) * cs);
-    const size_t partial = al256((size_t)nfields * batch * nt * (loss_ntiles(p) + 1) * sizeof(double));   // tiles + the per-time sums
+    const size_t planes = align256((size_t)nfields * batch * nt * p->n * loss_ldk(p) * cs);
+    const size_t partial = align256((size_t)nfields * batch * nt * (loss_ntiles(p) + 1) * sizeof(double));   // tiles + the per-time sums
     return planes + partial;
 }
 
@@ -414,20 +412,6 @@ static bool rows_geometry(int nt, int F, int* P_, int* NS_, unsigned* per_, size
     return true;
 }
 
-// the dynamic-LDS attribute of a kernel is set once per (kernel instantiation, device)
-template <typename K>
-static int raise_lds(K kernel, size_t bytes) {
-    static std::atomic<unsigned long long> done{0};     // one per instantiation of this template = per kernel
-    if (bytes <= 48 * 1024) return 0;
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (done.load(std::memory_order_acquire) & bit) return 0;
-    HIP_TRY(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    done.fetch_or(bit, std::memory_order_release);
-    return 0;
-}
-
 template <typename T, int N>
 static int loss_impl(const tcfd_loss_plan* p, const void* x, const void* y, const void* w2, long batch, int nt, int F,
                      int relative, int mesh_weighted, int time_average, int reduction, void* out, void* sums, void* ws,
@@ -441,7 +425,7 @@ static int loss_impl(const tcfd_loss_plan* p, const void* x, const void* y, cons
     if (!rows_geometry<T, N>(nt, F, &P, &NS, &per, &lds1))
         return FAIL(TCFD_EINVAL, "sobolev_loss: %d time steps of a %d-point row do not fit one workgroup", nt, N);
     cf* planes = (cf*)ws;
-    double* partial = (double*)((unsigned char*)ws + al256((size_t)F * batch * nt * N * ldk * sizeof(cf)));
+    double* partial = (double*)((unsigned char*)ws + align256((size_t)F * batch * nt * N * ldk * sizeof(cf)));
     const long slabs = batch * N;
     int rc;
     {

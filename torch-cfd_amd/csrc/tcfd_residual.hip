@@ -32,7 +32,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -492,21 +491,6 @@ __global__ __launch_bounds__(ROW_THREADS) void k_res_rows_bwd(const cx<T>* __res
 }
 
 // ------------------------------------------------------------------ host side of the residual
-static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-template <typename K>
-static int raise_lds(K kernel, size_t bytes) {
-    static std::atomic<unsigned long long> done{0};     // one per instantiation of this template = per kernel
-    if (bytes <= 48 * 1024) return 0;
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (done.load(std::memory_order_acquire) & bit) return 0;
-    HIP_TRY(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    done.fetch_or(bit, std::memory_order_release);
-    return 0;
-}
-
 struct ResLayout {
     size_t plane_bytes;    // one complex plane set (b, t, n, n), 256-byte aligned
     size_t partial_off;    // doubles (b, t, ntiles, n)
@@ -518,13 +502,12 @@ static ResLayout res_layout(const tcfd_loss_plan* p, long batch, int nt, int bac
     const size_t cs = p->dtype == TCFD_C128 ? 16 : 8;
     const int C = p->dtype == TCFD_C128 ? 8 : 16;
     L.ntiles = p->n / C;
-    L.plane_bytes = al256((size_t)batch * nt * p->n * p->n * cs);
+    L.plane_bytes = align256((size_t)batch * nt * p->n * p->n * cs);
     L.partial_off = (size_t)(backward ? 6 : 5) * L.plane_bytes;
-    L.total = L.partial_off + al256((size_t)batch * nt * L.ntiles * p->n * sizeof(double));
+    L.total = L.partial_off + align256((size_t)batch * nt * L.ntiles * p->n * sizeof(double));
     return L;
 }
 
-#if !defined(TCFD_RES_UNIT) || TCFD_RES_UNIT == 0
 extern "C" size_t tcfd_residual_workspace_bytes(const tcfd_loss_plan* p, long batch, int nt, int backward) {
     if (!p || batch <= 0 || nt <= 0) return 0;
     return res_layout(p, batch, nt, backward).total;
@@ -533,7 +516,6 @@ extern "C" size_t tcfd_residual_workspace_bytes(const tcfd_loss_plan* p, long ba
 extern "C" int tcfd_residual_loss_supported(const tcfd_loss_plan* p, int nt) {
     return (p && nt >= 1 && nt <= RES_MAX_NT) ? 1 : 0;
 }
-#endif
 
 struct ResArgs {
     const void *w, *f, *m2pi, *lap, *ckt, *twt;
@@ -699,11 +681,6 @@ static int res_bwd_dispatch(const tcfd_loss_plan* p, const ResArgs& a, const voi
     return FAIL(TCFD_EINVAL, "residual_loss_backward: unsupported n = %d", p->n);
 }
 
-#if !defined(TCFD_RES_UNIT) || TCFD_RES_UNIT == 0
-int tcfd_res_fwd_f32(const tcfd_loss_plan* p, const ResArgs& a, void* out, void* rows, void* ws, hipStream_t st);
-int tcfd_res_bwd_f32(const tcfd_loss_plan* p, const ResArgs& a, const void* rows, const void* gout, void* gw, void* gf, void* ws,
-                     hipStream_t st);
-
 extern "C" int tcfd_residual_loss(const tcfd_loss_plan* p, const void* w, const void* f, const void* mk2pi, const void* lap,
                                   const void* ckt, const void* twt, double visc, double scale, long batch, int nt, void* out,
                                   void* rows, void* ws, size_t ws_bytes, void* stream) {
@@ -713,7 +690,7 @@ extern "C" int tcfd_residual_loss(const tcfd_loss_plan* p, const void* w, const 
     if (ws_bytes < need) return FAIL(TCFD_EWORKSPACE, "workspace %zu B < required %zu B", ws_bytes, need);
     const ResArgs a{w, f, mk2pi, lap, ckt, twt, visc, scale, batch, nt};
     if (p->dtype == TCFD_C128) return res_fwd_dispatch<double>(p, a, out, rows, ws, (hipStream_t)stream);
-    return tcfd_res_fwd_f32(p, a, out, rows, ws, (hipStream_t)stream);
+    return res_fwd_dispatch<float>(p, a, out, rows, ws, (hipStream_t)stream);
 }
 
 extern "C" int tcfd_residual_loss_backward(const tcfd_loss_plan* p, const void* w, const void* f, const void* mk2pi,
@@ -728,19 +705,9 @@ extern "C" int tcfd_residual_loss_backward(const tcfd_loss_plan* p, const void* 
     if (ws_bytes < need) return FAIL(TCFD_EWORKSPACE, "workspace %zu B < required %zu B", ws_bytes, need);
     const ResArgs a{w, f, mk2pi, lap, ckt, twt, visc, scale, batch, nt};
     if (p->dtype == TCFD_C128) return res_bwd_dispatch<double>(p, a, rows, gout, grad_w, grad_f, ws, (hipStream_t)stream);
-    return tcfd_res_bwd_f32(p, a, rows, gout, grad_w, grad_f, ws, (hipStream_t)stream);
+    return res_bwd_dispatch<float>(p, a, rows, gout, grad_w, grad_f, ws, (hipStream_t)stream);
 }
-#else
-int tcfd_res_fwd_f32(const tcfd_loss_plan* p, const ResArgs& a, void* out, void* rows, void* ws, hipStream_t st) {
-    return res_fwd_dispatch<float>(p, a, out, rows, ws, st);
-}
-int tcfd_res_bwd_f32(const tcfd_loss_plan* p, const ResArgs& a, const void* rows, const void* gout, void* gw, void* gf, void* ws,
-                     hipStream_t st) {
-    return res_bwd_dispatch<float>(p, a, rows, gout, gw, gf, ws, st);
-}
-#endif
 
-#if !defined(TCFD_RES_UNIT) || TCFD_RES_UNIT == 0
 // ===================================================================== p-norm sums
 // x, y viewed as (outer, reduce, inner), contiguous.  sd[o][i] = sum_r |x - y|^p (y may be null: |x|^p), sy[o][i] = sum_r |y|^p
 // (when asked).  Stage 1: `nblk` workgroups per outer index walk equal contiguous shares; a lane keeps its `inner` index (the
@@ -834,7 +801,7 @@ static int lp_nblk(long reduce, int inner) {
 
 extern "C" size_t tcfd_lp_sums_workspace_bytes(long outer, long reduce, int inner) {
     if (outer <= 0 || reduce <= 0 || inner <= 0) return 0;
-    return al256((size_t)outer * lp_nblk(reduce, inner) * 2 * inner * sizeof(double));
+    return align256((size_t)outer * lp_nblk(reduce, inner) * 2 * inner * sizeof(double));
 }
 
 extern "C" int tcfd_lp_sums(const void* x, const void* y, void* sum_diff, void* sum_y, long outer, long reduce, int inner, double p,
@@ -966,7 +933,7 @@ static int h1_nblk(long per) {
 
 extern "C" size_t tcfd_h1_sums_workspace_bytes(long batch, int channels, int n1, int n2) {
     if (batch <= 0 || channels <= 0 || n1 <= 0 || n2 <= 0) return 0;
-    return al256((size_t)batch * h1_nblk((long)channels * n1 * n2) * 2 * sizeof(double));
+    return align256((size_t)batch * h1_nblk((long)channels * n1 * n2) * 2 * sizeof(double));
 }
 
 extern "C" int tcfd_h1_sums(const void* preds, const void* tgrad, const void* ksqrt, int kmode, void* s1, void* s2, long batch,
@@ -1010,4 +977,3 @@ extern "C" int tcfd_h1_sums_bwd(const void* preds, const void* tgrad, const void
     HIP_TRY(hipGetLastError());
     return 0;
 }
-#endif
