@@ -93,8 +93,8 @@ const char* tcfd_last_error(void);
  * tcfd_lp_sums_bwd, tcfd_lp_sums_workspace_bytes, tcfd_h1_sums, tcfd_h1_sums_bwd, tcfd_h1_sums_workspace_bytes;
  * 13: tcfd_fvm_plan_set_advection and the TCFD_FVM_* advection schemes; no earlier entry point changed).
  * The tcfd_data_* entry points and the tangent-linear ones (tcfd_ns2d_explicit_terms_jvp, tcfd_ns2d_step_jvp,
- * tcfd_ns2d_jvp_workspace_bytes) were ADDED under revision 13 without a new number (no argument list or meaning of an existing
- * entry changed); a host that needs them looks the symbols up, as torch-cfd_amd/datasets.py and _HipPlan.jvp_workspace do.  A host compares it with the TCFD_ABI_VERSION it was written against BEFORE the
+ * tcfd_ns2d_jvp_workspace_bytes) and tcfd_fvm_plan_set_tangent were ADDED under revision 13 without a new number (no argument
+ * list or meaning of an existing entry changed: a plan keeps its behaviour until the new call turns the flag on); a host that needs them looks the symbols up, as torch-cfd_amd/datasets.py and _HipPlan.jvp_workspace do.  A host compares it with the TCFD_ABI_VERSION it was written against BEFORE the
  * first call: a stale prebuilt library would otherwise be called with the wrong argument layout and return garbage
  * (torch-cfd_amd/_lib.py::load does). */
 int tcfd_version(void);
@@ -662,6 +662,20 @@ size_t tcfd_fvm_step_vjp_workspace_bytes(const tcfd_fvm_plan* plan, long batch);
 int tcfd_fvm_step_vjp(const tcfd_fvm_plan* plan, const void* saved, const void* gx, const void* gy, void* out_x, void* out_y,
                       long batch, int steps, int nstages, const double* a, const double* b, double dt, void* workspace,
                       size_t workspace_bytes, void* stream);
+
+/* Jacobian-vector products of the finite-volume solver (forward mode, the tangent-linear model).
+ * A tangent plan steps PAIRS: every call takes batch = 2 B fields per component, fields [0, B) the state,
+ * fields [B, 2 B) its perturbation, in every input and output array (field b + B is the perturbation of field b).
+ *   tcfd_fvm_explicit_terms: [u; du] -> [F(u); J_F(u) du].  The tangent carries the Laplacian and the drag of du and no forcing.
+ *   tcfd_fvm_step: `steps` RK steps of the state and of its tangent, all stages and projections of all steps in one call;
+ *     steps == 0 copies both halves.  Workspace: tcfd_fvm_workspace_bytes(plan, 2 B), as for any batch of 2 B fields.
+ *   tcfd_fvm_project is linear and acts on every field alike: the same with or without the flag.
+ * The state half is bit-equal to the same call of a plain plan on the B state fields.  The derivatives follow the branches
+ * torch's forward mode takes through the reference's ops (the conventions of the VJP above).
+ * On a tangent plan an odd batch returns TCFD_EINVAL, and so do tcfd_fvm_explicit_terms_vjp and tcfd_fvm_step_vjp (forward
+ * over reverse is not provided).  `on` other than 0 or 1 returns TCFD_EINVAL and leaves the plan as it was; every case names
+ * itself in tcfd_last_error.  A plan without the flag (a fresh plan; on = 0) behaves as before this entry point existed. */
+int tcfd_fvm_plan_set_tangent(tcfd_fvm_plan* plan, int on);
 
 /* ---- Gaussian random field: half spectrum of the (sub-sampled) sample, no transform -------------------------------
  * Replaces GRF2d.sample of fno/data_gen/grf.py:79-115 followed by the driver's nearest sub-sampling and rfft2

@@ -226,6 +226,7 @@ SIGNATURES = {
     "tcfd_fvm_plan_create": (_i, [ctypes.POINTER(_vp), _i, _i, _d, _d, _d, _dp, _dp, _dp]),
     "tcfd_fvm_plan_destroy": (None, [_vp]),
     "tcfd_fvm_plan_set_advection": (_i, [_vp, _i]),
+    "tcfd_fvm_plan_set_tangent": (_i, [_vp, _i]),
     "tcfd_fvm_workspace_bytes": (_sz, [_vp, _l]),
     "tcfd_fvm_explicit_terms": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _d, _vp]),
     "tcfd_fvm_project": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _vp, _sz, _vp]),

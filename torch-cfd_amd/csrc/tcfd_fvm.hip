@@ -19,6 +19,11 @@
 //   for i = s-1 .. 0:  k_fvm_stage_vjp  g_i = J_F(u_i)^T kbar_i  (i = 0: added into u_bar; done)
 //                      projection of g_i, k_fvm_apply_adj: mu_i = P g_i;  u_bar += mu_i;  kbar_j (+)= a_ij mu_i (j < i)
 //
+// Tangent-linear step (a plan with tcfd_fvm_plan_set_tangent on): every field array holds PAIRS, fields [0, B) the state and
+// fields [B, 2 B) its perturbation.  k_fvm_stage_jvp replaces k_fvm_stage and runs over the B samples: it forms k = F(u) by the
+// state kernel's own code and dk = J_F(u) du from the same stencil, and writes the RK targets of both halves.  Every other pass
+// (k_fvm_div, the transforms, k_fvm_mul, k_fvm_apply) is linear per field and runs unchanged over the 2 B fields.
+//
 // Every arithmetic expression restates the reference's operation order; floating-point contraction is off in this file
 // so that a * b + c rounds twice as the reference's tensor ops do.
 #include <hip/hip_runtime.h>
@@ -244,6 +249,176 @@ __global__ void __launch_bounds__(256) k_fvm_stage(const T* __restrict__ ux, con
         }
         tg.x[t][p] = px;
         tg.y[t][p] = py;
+    }
+}
+
+// ---------------------------------------------------------------- tangent (Jacobian-vector products)
+// Tangent of tvd_flux along (dcm, dc0, dc1, dc2, dw), by the branches torch's forward mode takes through the reference's ops,
+// the conventions of tvd_flux_vjp below: the selections w > 0 and r > 0 carry no tangent, w enters through the Courant number
+// and the final product ci * w, and the constant denominator 1 of safe_div (d == 0; 1 + r == 0 lies in the arm r > 0 never
+// selects) has zero tangent.  Every term is a product of one tangent with state values, so the result is linear in the tangent
+// bit for bit under a scaling by a power of two, and exactly zero for a zero tangent.
+template <typename T>
+__device__ __forceinline__ T tvd_flux_jvp(T cm, T c0, T c1, T c2, T w, T dcm, T dc0, T dc1, T dc2, T dw, T cfl) {
+    const bool pos = w > T(0);
+    const T clow = pos ? c0 : c1;
+    const T dclow = pos ? dc0 : dc1;
+    const T cr = cfl * w;
+    const T d = c1 - c0;
+    const T dd = dc1 - dc0;
+    const T alpha = T(0.5) * (T(1) - cr);   // hp = c0 + alpha d
+    const T beta = T(0.5) * (T(1) + cr);    // hn = c1 - beta d
+    const T chigh = pos ? c0 + alpha * d : c1 - beta * d;
+    // d chigh / d w = -cfl d / 2 in both branches
+    const T dchigh = (pos ? dc0 + alpha * dd : dc1 - beta * dd) - (T(0.5) * (cfl * dw)) * d;
+    const bool dnz = d != T(0);
+    const T den = dnz ? d : T(1);
+    const T dden = dnz ? dd : T(0);
+    const T r = (pos ? c0 - cm : c2 - c1) / den;
+    const T dr = ((pos ? dc0 - dcm : dc2 - dc1) - r * dden) / den;
+    const bool lim = r > T(0);
+    const T rp1 = T(1) + r;
+    const T phi = lim ? (T(2) * r) / rp1 : T(0);
+    const T dphi = lim ? (T(2) * dr - phi * dr) / rp1 : T(0);
+    const T ci = clow - (clow - chigh) * phi;
+    const T dci = dclow - ((dclow - dchigh) * phi + (clow - chigh) * dphi);
+    return dci * w + ci * dw;
+}
+
+// tangent of face_flux along (dc0, dc1, dw), by the same rules
+template <int SCHEME, typename T>
+__device__ __forceinline__ T face_flux_jvp(T c0, T c1, T w, T dc0, T dc1, T dw, T cfl) {
+    static_assert(SCHEME == UPWIND || SCHEME == LINEAR || SCHEME == LAX_WENDROFF, "two-cell schemes only");
+    if constexpr (SCHEME == UPWIND) {
+        const bool pos = w > T(0);
+        return (pos ? dc0 : dc1) * w + (pos ? c0 : c1) * dw;
+    } else if constexpr (SCHEME == LINEAR) {
+        return half(dc0, dc1) * w + half(c0, c1) * dw;
+    } else {
+        const bool pos = w > T(0);
+        const T cr = cfl * w;
+        const T d = c1 - c0;
+        const T dd = dc1 - dc0;
+        const T alpha = T(0.5) * (T(1) - cr);
+        const T beta = T(0.5) * (T(1) + cr);
+        const T ci = pos ? c0 + alpha * d : c1 - beta * d;
+        const T dci = (pos ? dc0 + alpha * dd : dc1 - beta * dd) - (T(0.5) * (cfl * dw)) * d;
+        return dci * w + ci * dw;
+    }
+}
+
+// (dkx, dky) = J (DX, DY) of explicit_point at cell (i, j): X / Y the state, DX / DY its perturbation.  The faces, their
+// arguments and the order of the sums are explicit_point's, each flux replaced by its tangent; the Laplacian and the drag act on
+// the perturbation, and the forcing, which does not depend on the state, drops out.  The state loads repeat the addresses
+// explicit_point reads, so next to it in one kernel they are loaded once.  As there, the two-cell schemes never form the +-2
+// addresses, of X and Y or of DX and DY.
+template <int SCHEME, typename T>
+__device__ __forceinline__ void explicit_point_jvp(const T* __restrict__ X, const T* __restrict__ Y, const T* __restrict__ DX,
+                                                   const T* __restrict__ DY, int i, int j, int n, const StageConst<T>& s, T& dkx,
+                                                   T& dky) {
+    auto at = [n](const T* p, int a, int b) { return p[(size_t)a * n + b]; };
+    const int im1 = wrap(i - 1, n), ip1 = wrap(i + 1, n);
+    const int jm1 = wrap(j - 1, n), jp1 = wrap(j + 1, n);
+    const T x00 = at(X, i, j), xm1 = at(X, im1, j), xp1 = at(X, ip1, j), xjm1 = at(X, i, jm1), xjp1 = at(X, i, jp1);
+    const T y00 = at(Y, i, j), ym1 = at(Y, im1, j), yp1 = at(Y, ip1, j), yjm1 = at(Y, i, jm1), yjp1 = at(Y, i, jp1);
+    const T yp1jm1 = at(Y, ip1, jm1), xm1jp1 = at(X, im1, jp1);
+    const T dx00 = at(DX, i, j), dxm1 = at(DX, im1, j), dxp1 = at(DX, ip1, j), dxjm1 = at(DX, i, jm1), dxjp1 = at(DX, i, jp1);
+    const T dy00 = at(DY, i, j), dym1 = at(DY, im1, j), dyp1 = at(DY, ip1, j), dyjm1 = at(DY, i, jm1), dyjp1 = at(DY, i, jp1);
+    const T dyp1jm1 = at(DY, ip1, jm1), dxm1jp1 = at(DX, im1, jp1);
+    T dadv_x, dadv_y;
+    if constexpr (SCHEME == VAN_LEER) {
+        const int im2 = wrap(i - 2, n), ip2 = wrap(i + 2, n), jm2 = wrap(j - 2, n), jp2 = wrap(j + 2, n);
+        const T xm2 = at(X, im2, j), xp2 = at(X, ip2, j), xjm2 = at(X, i, jm2), xjp2 = at(X, i, jp2);
+        const T ym2 = at(Y, im2, j), yp2 = at(Y, ip2, j), yjm2 = at(Y, i, jm2), yjp2 = at(Y, i, jp2);
+        const T dxm2 = at(DX, im2, j), dxp2 = at(DX, ip2, j), dxjm2 = at(DX, i, jm2), dxjp2 = at(DX, i, jp2);
+        const T dym2 = at(DY, im2, j), dyp2 = at(DY, ip2, j), dyjm2 = at(DY, i, jm2), dyjp2 = at(DY, i, jp2);
+        {
+            const T f_hi = tvd_flux_jvp(xm1, x00, xp1, xp2, half(x00, xp1), dxm1, dx00, dxp1, dxp2, half(dx00, dxp1), s.cfl);
+            const T f_lo = tvd_flux_jvp(xm2, xm1, x00, xp1, half(xm1, x00), dxm2, dxm1, dx00, dxp1, half(dxm1, dx00), s.cfl);
+            const T g_hi = tvd_flux_jvp(xjm1, x00, xjp1, xjp2, half(y00, yp1), dxjm1, dx00, dxjp1, dxjp2, half(dy00, dyp1), s.cfl);
+            const T g_lo = tvd_flux_jvp(xjm2, xjm1, x00, xjp1, half(yjm1, yp1jm1), dxjm2, dxjm1, dx00, dxjp1,
+                                        half(dyjm1, dyp1jm1), s.cfl);
+            dadv_x = -((f_hi - f_lo) / s.h + (g_hi - g_lo) / s.h);
+        }
+        {
+            const T f_hi = tvd_flux_jvp(ym1, y00, yp1, yp2, half(x00, xjp1), dym1, dy00, dyp1, dyp2, half(dx00, dxjp1), s.cfl);
+            const T f_lo = tvd_flux_jvp(ym2, ym1, y00, yp1, half(xm1, xm1jp1), dym2, dym1, dy00, dyp1, half(dxm1, dxm1jp1),
+                                        s.cfl);
+            const T g_hi = tvd_flux_jvp(yjm1, y00, yjp1, yjp2, half(y00, yjp1), dyjm1, dy00, dyjp1, dyjp2, half(dy00, dyjp1), s.cfl);
+            const T g_lo = tvd_flux_jvp(yjm2, yjm1, y00, yjp1, half(yjm1, y00), dyjm2, dyjm1, dy00, dyjp1, half(dyjm1, dy00), s.cfl);
+            dadv_y = -((f_hi - f_lo) / s.h + (g_hi - g_lo) / s.h);
+        }
+    } else {
+        {
+            const T f_hi = face_flux_jvp<SCHEME>(x00, xp1, half(x00, xp1), dx00, dxp1, half(dx00, dxp1), s.cfl);
+            const T f_lo = face_flux_jvp<SCHEME>(xm1, x00, half(xm1, x00), dxm1, dx00, half(dxm1, dx00), s.cfl);
+            const T g_hi = face_flux_jvp<SCHEME>(x00, xjp1, half(y00, yp1), dx00, dxjp1, half(dy00, dyp1), s.cfl);
+            const T g_lo = face_flux_jvp<SCHEME>(xjm1, x00, half(yjm1, yp1jm1), dxjm1, dx00, half(dyjm1, dyp1jm1), s.cfl);
+            dadv_x = -((f_hi - f_lo) / s.h + (g_hi - g_lo) / s.h);
+        }
+        {
+            const T f_hi = face_flux_jvp<SCHEME>(y00, yp1, half(x00, xjp1), dy00, dyp1, half(dx00, dxjp1), s.cfl);
+            const T f_lo = face_flux_jvp<SCHEME>(ym1, y00, half(xm1, xm1jp1), dym1, dy00, half(dxm1, dxm1jp1), s.cfl);
+            const T g_hi = face_flux_jvp<SCHEME>(y00, yjp1, half(y00, yjp1), dy00, dyjp1, half(dy00, dyjp1), s.cfl);
+            const T g_lo = face_flux_jvp<SCHEME>(yjm1, y00, half(yjm1, y00), dyjm1, dy00, half(dyjm1, dy00), s.cfl);
+            dadv_y = -((f_hi - f_lo) / s.h + (g_hi - g_lo) / s.h);
+        }
+    }
+    // finish_point on the perturbation, without the forcing
+    finish_point(Near<T>{dx00, dxm1, dxp1, dxjm1, dxjp1, dy00, dym1, dyp1, dyjm1, dyjp1}, dadv_x, dadv_y, (const T*)nullptr,
+                 (const T*)nullptr, i, j, n, s, dkx, dky);
+}
+
+// k_fvm_stage on a pair: fields [0, B) of every array the state, fields [B, 2 B) the perturbation, `pair` = B n^2 elements
+// apart.  One thread per cell of the B samples; blockIdx.z = sample.  The state half is k_fvm_stage's own code (explicit_point,
+// the same target expressions), so it is bit-equal to the plain kernel; the tangent half writes (du0, dk) to the same targets
+// with the same modes and weights.
+template <int SCHEME, typename T>
+__global__ void __launch_bounds__(256) k_fvm_stage_jvp(const T* __restrict__ ux, const T* __restrict__ uy, const T* __restrict__ u0x,
+                                                       const T* __restrict__ u0y, const T* __restrict__ fx, const T* __restrict__ fy,
+                                                       T* __restrict__ kx_out, T* __restrict__ ky_out, Targets<T> tg, StageConst<T> s,
+                                                       int n, size_t pair) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = blockIdx.y * blockDim.y + threadIdx.y;
+    if (i >= n || j >= n) return;
+    const size_t plane = (size_t)n * n;
+    const size_t base = (size_t)blockIdx.z * plane;
+    T kx, ky, dkx, dky;
+    explicit_point<SCHEME>(ux + base, uy + base, fx, fy, i, j, n, s, kx, ky);
+    explicit_point_jvp<SCHEME>(ux + base, uy + base, ux + pair + base, uy + pair + base, i, j, n, s, dkx, dky);
+    const size_t p = base + (size_t)i * n + j;
+    const size_t dp = pair + p;
+    if (kx_out) {
+        kx_out[p] = kx;
+        ky_out[p] = ky;
+        kx_out[dp] = dkx;
+        ky_out[dp] = dky;
+    }
+    for (int t = 0; t < tg.count; ++t) {
+        const int mode = tg.mode[t];
+        const T c = tg.c[t];
+        T px, py, dpx, dpy;
+        if (mode == 2) {
+            px = tg.x[t][p];
+            py = tg.y[t][p];
+            dpx = tg.x[t][dp];
+            dpy = tg.y[t][dp];
+        } else {
+            px = u0x[p];
+            py = u0y[p];
+            dpx = u0x[dp];
+            dpy = u0y[dp];
+        }
+        if (mode != 3) {
+            px = px + kx * c;
+            py = py + ky * c;
+            dpx = dpx + dkx * c;
+            dpy = dpy + dky * c;
+        }
+        tg.x[t][p] = px;
+        tg.y[t][p] = py;
+        tg.x[t][dp] = dpx;
+        tg.y[t][dp] = dpy;
     }
 }
 
@@ -577,6 +752,7 @@ struct tcfd_fvm_plan {
     void* fy;
     size_t fft_ws;             // tcfd_ns2d_workspace_bytes of the transform plan, per batch, computed at call time
     int scheme;                // TCFD_FVM_*: the instantiation of k_fvm_stage / k_fvm_stage_vjp, read at every launch
+    int tangent;               // 1: every call carries pairs, fields [0, B) the state and [B, 2 B) its perturbation
 };
 
 namespace {
@@ -611,10 +787,18 @@ int stage_launch(const tcfd_fvm_plan* p, const void* ux, const void* uy, const v
         tg.c[t] = t < count ? (T)c[t] : T(0);
         tg.mode[t] = t < count ? mode[t] : 0;
     }
+    // a tangent plan: the pair kernel over the B = batch / 2 samples, the perturbation B planes after the state
+    const long half_batch = batch / 2;
+    const size_t pair = (size_t)half_batch * p->n * p->n;
 #define STAGE(SCHEME)                                                                                                      \
-    hipLaunchKernelGGL((k_fvm_stage<SCHEME, T>), cell_grid(p->n, batch), kCellBlock, 0, st, (const T*)ux, (const T*)uy,    \
-                       (const T*)u0x, (const T*)u0y, (const T*)p->fx, (const T*)p->fy, (T*)kx, (T*)ky, tg,                 \
-                       stage_const<T>(p, dt), p->n)
+    if (p->tangent)                                                                                                        \
+        hipLaunchKernelGGL((k_fvm_stage_jvp<SCHEME, T>), cell_grid(p->n, half_batch), kCellBlock, 0, st, (const T*)ux,     \
+                           (const T*)uy, (const T*)u0x, (const T*)u0y, (const T*)p->fx, (const T*)p->fy, (T*)kx, (T*)ky,   \
+                           tg, stage_const<T>(p, dt), p->n, pair);                                                         \
+    else                                                                                                                   \
+        hipLaunchKernelGGL((k_fvm_stage<SCHEME, T>), cell_grid(p->n, batch), kCellBlock, 0, st, (const T*)ux,              \
+                           (const T*)uy, (const T*)u0x, (const T*)u0y, (const T*)p->fx, (const T*)p->fy, (T*)kx, (T*)ky,   \
+                           tg, stage_const<T>(p, dt), p->n)
     switch (p->scheme) {
         case VAN_LEER: STAGE(VAN_LEER); break;
         case UPWIND: STAGE(UPWIND); break;
@@ -853,6 +1037,13 @@ int tcfd_fvm_plan_set_advection(tcfd_fvm_plan* p, int scheme) {
     return 0;
 }
 
+int tcfd_fvm_plan_set_tangent(tcfd_fvm_plan* p, int on) {
+    if (on != 0 && on != 1) return FAIL(TCFD_EINVAL, "fvm_plan_set_tangent: on = %d (0: plain plan, 1: tangent plan)", on);
+    if (!p) return FAIL(TCFD_EINVAL, "fvm_plan_set_tangent: null plan");
+    p->tangent = on;
+    return 0;
+}
+
 size_t tcfd_fvm_workspace_bytes(const tcfd_fvm_plan* p, long batch) {
     if (!p || batch <= 0) return 0;
     return carve(p, batch, nullptr, kStep).total;
@@ -861,6 +1052,8 @@ size_t tcfd_fvm_workspace_bytes(const tcfd_fvm_plan* p, long batch) {
 int tcfd_fvm_explicit_terms(const tcfd_fvm_plan* p, const void* ux, const void* uy, void* kx, void* ky, long batch,
                                          double dt, void* stream) {
     if (!p || !ux || !uy || !kx || !ky || batch <= 0) return FAIL(TCFD_EINVAL, "fvm_explicit_terms: bad argument");
+    if (p->tangent && batch % 2)
+        return FAIL(TCFD_EINVAL, "fvm_explicit_terms: batch %ld on a tangent plan, which takes pairs (batch = 2 B)", batch);
     return stage_launch(p, ux, uy, ux, uy, kx, ky, nullptr, nullptr, nullptr, nullptr, 0, batch, dt, (hipStream_t)stream);
 }
 
@@ -880,6 +1073,8 @@ int tcfd_fvm_step(const tcfd_fvm_plan* p, const void* ux_in, const void* uy_in, 
                                size_t ws_bytes, void* stream) {
     if (!p || !ux_in || !uy_in || !ux_out || !uy_out || batch <= 0 || steps < 0 || !b || (nstages > 1 && !a))
         return FAIL(TCFD_EINVAL, "fvm_step: bad argument");
+    if (p->tangent && batch % 2)
+        return FAIL(TCFD_EINVAL, "fvm_step: batch %ld on a tangent plan, which takes pairs (batch = 2 B)", batch);
     if (nstages < 1 || nstages > MAXT) return FAIL(TCFD_EINVAL, "fvm_step: %d stages (1 .. %d supported)", nstages, MAXT);
     for (int i = 0; i < nstages; ++i)
         for (int j = i; j < nstages; ++j)
@@ -945,6 +1140,7 @@ int tcfd_fvm_explicit_terms_vjp(const tcfd_fvm_plan* p, const void* ux, const vo
                                 void* out_x, void* out_y, long batch, double dt, void* stream) {
     if (!p || !ux || !uy || !gx || !gy || !out_x || !out_y || batch <= 0)
         return FAIL(TCFD_EINVAL, "fvm_explicit_terms_vjp: bad argument");
+    if (p->tangent) return FAIL(TCFD_EINVAL, "fvm_explicit_terms_vjp: a tangent plan (forward over reverse is not provided)");
     if (out_x == gx || out_x == gy || out_y == gx || out_y == gy || out_x == ux || out_x == uy || out_y == ux || out_y == uy)
         return FAIL(TCFD_EINVAL, "fvm_explicit_terms_vjp: the output may not alias an input (the stencil reads neighbours)");
     return stage_vjp_launch(p, ux, uy, gx, gy, out_x, out_y, 0, batch, dt, (hipStream_t)stream);
@@ -960,6 +1156,7 @@ int tcfd_fvm_step_vjp(const tcfd_fvm_plan* p, const void* saved, const void* gx,
                       void* stream) {
     if (!p || !gx || !gy || !out_x || !out_y || batch <= 0 || steps < 0 || (steps > 0 && !saved) || !b || (nstages > 1 && !a))
         return FAIL(TCFD_EINVAL, "fvm_step_vjp: bad argument");
+    if (p->tangent) return FAIL(TCFD_EINVAL, "fvm_step_vjp: a tangent plan (forward over reverse is not provided)");
     if (nstages < 1 || nstages > MAXT) return FAIL(TCFD_EINVAL, "fvm_step_vjp: %d stages (1 .. %d supported)", nstages, MAXT);
     for (int i = 0; i < nstages; ++i)
         for (int j = i; j < nstages; ++j)

@@ -17,6 +17,13 @@ fp64, 4 for fp32), until its backward has run.  A tableau whose parameters requi
 The advection scheme is the equation's ``convect`` argument: ``convect`` (van Leer, the default) or
 ``advection(interpolation.upwind | linear | lax_wendroff)``, the counterparts of the reference's ``convect`` and of an
 ``advect_general`` with that ``c_interpolation_fn``.  Each is one instantiation of the stage kernel and of its adjoint.
+
+Forward mode: ``explicit_terms_jvp(u, du, dt)`` and ``tangent_step(u, du, dt, steps)`` carry a perturbation ``du`` of the
+state through the tangent instantiation of the stage kernel (``k_fvm_stage_jvp``), on a tangent plan
+(``tcfd_fvm_plan_set_tangent``) that steps the stacked pair ``[u; du]`` in one library call.  A dual number of
+``torch.autograd.forward_ad`` given to ``forward`` / ``advance``, ``RKStepper.forward``, ``explicit_terms``, ``convect``,
+``pressure_projection`` / ``PressureProjection.forward`` or ``get_trajectory_fvm`` runs the same calls; a component without a
+tangent counts as a zero tangent.  Forward over reverse is not provided.
 """
 from __future__ import annotations
 
@@ -27,6 +34,7 @@ from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
+import torch.autograd.forward_ad as fwAD
 import torch.nn as nn
 
 from . import _lib
@@ -49,6 +57,38 @@ def _as_pair(u) -> Tuple[torch.Tensor, torch.Tensor]:
         raise ValueError(f"velocity components differ: {tuple(ux.shape)} {ux.dtype} {ux.device} vs "
                          f"{tuple(uy.shape)} {uy.dtype} {uy.device}")
     return ux, uy
+
+
+def _unpack_duals(ux: torch.Tensor, uy: torch.Tensor):
+    """``None`` for plain tensors; for forward-mode dual numbers ``((ux, uy), (dux, duy))``, the primals and the tangents, a
+    component without a tangent counting as a zero tangent."""
+    (px, tx), (py, ty) = fwAD.unpack_dual(ux), fwAD.unpack_dual(uy)
+    if tx is None and ty is None:
+        return None
+    tx = torch.zeros_like(px) if tx is None else tx
+    ty = torch.zeros_like(py) if ty is None else ty
+    return (px, py), (tx, ty)
+
+
+def _make_duals(out, dout):
+    return tuple(fwAD.make_dual(o, d) for o, d in zip(out, dout))
+
+
+def _jvp_pairs(u, du, n: int, what: str):
+    """The checks the tangent-linear entry points share, before any device call: shapes and dtypes (ValueError), then
+    gradients (forward over reverse is not implemented).  Returns ``((ux, uy), (dux, duy))``."""
+    ux, uy = _as_pair(u)
+    dux, duy = _as_pair(du)
+    if dux.shape != ux.shape or dux.dtype != ux.dtype or dux.device != ux.device:
+        raise ValueError(f"{what}: the tangent must have the shape and dtype of the state, got {tuple(dux.shape)} {dux.dtype} "
+                         f"{dux.device} for {tuple(ux.shape)} {ux.dtype} {ux.device}")
+    if ux.ndim not in (2, 3) or tuple(ux.shape[-2:]) != (n, n) or ux.dtype not in _FP:
+        raise ValueError(f"{what}: expected float64 or float32 (n, n) or (B, n, n) velocity components with n = {n}, got "
+                         f"{tuple(ux.shape)} {ux.dtype}")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (ux, uy, dux, duy)):
+        raise NotImplementedError(f"{what}: forward mode over reverse mode is not implemented -- the state or its tangent "
+                                  "requires grad in grad mode; detach them or differentiate with the reverse-mode path alone")
+    return (ux, uy), (dux, duy)
 
 
 def _check_periodic(bcs) -> None:
@@ -220,7 +260,7 @@ class _FvmPlan:
 
     def __init__(self, n: int, dtype: torch.dtype, device: torch.device, h: float, nu: float, drag: float,
                  inverse: torch.Tensor, force: Optional[Tuple[torch.Tensor, torch.Tensor]],
-                 scheme: int = _lib.TCFD_FVM_VAN_LEER):
+                 scheme: int = _lib.TCFD_FVM_VAN_LEER, tangent: bool = False):
         self.lib = _lib.load()
         self.n, self.dtype, self.device = n, dtype, torch.device(device)
         if self.device.type != "cuda":
@@ -243,6 +283,9 @@ class _FvmPlan:
         self._finalizer = weakref.finalize(self, self.lib.tcfd_fvm_plan_destroy, handle)
         self.scheme = int(scheme)   # fixed for the plan's life: a pending backward holds the plan and so its scheme
         _lib.check(self.lib.tcfd_fvm_plan_set_advection(handle, self.scheme), "tcfd_fvm_plan_set_advection")
+        self.tangent = bool(tangent)   # a tangent plan steps pairs [u; du]: its calls go through the *_pair methods below
+        if self.tangent:
+            _lib.check(self.lib.tcfd_fvm_plan_set_tangent(handle, 1), "tcfd_fvm_plan_set_tangent")
 
     def workspace(self, batch: int, need: Optional[int] = None) -> torch.Tensor:
         """At least ``need`` bytes (default: what ``tcfd_fvm_step`` needs for ``batch``)."""
@@ -294,6 +337,29 @@ class _FvmPlan:
                                         ws.data_ptr(), ws.numel(), self._stream())
         _lib.check(rc, "tcfd_fvm_step")
         return ox, oy
+
+    # ---- forward mode: the stacked pair [u; du] of a tangent plan (project: of any plan, the projection being linear)
+    @staticmethod
+    def _stack(u, du):
+        return torch.cat([u.reshape((-1,) + u.shape[-2:]), du.reshape((-1,) + du.shape[-2:])])
+
+    @staticmethod
+    def _split(ox, oy, shape):
+        b = ox.shape[0] // 2
+        return (ox[:b].reshape(shape), oy[:b].reshape(shape)), (ox[b:].reshape(shape), oy[b:].reshape(shape))
+
+    def explicit_terms_pair(self, ux, uy, dux, duy, dt: float):
+        """``((kx, ky), (dkx, dky))`` = ``(F(u), J_F(u) du)``, one launch of the tangent stage kernel."""
+        assert self.tangent
+        return self._split(*self.explicit_terms(self._stack(ux, dux), self._stack(uy, duy), dt), ux.shape)
+
+    def step_pair(self, ux, uy, dux, duy, dt: float, a: Sequence[float], b: Sequence[float], steps: int):
+        """``steps`` RK steps of the state and of its tangent in one library call."""
+        assert self.tangent
+        return self._split(*self.step(self._stack(ux, dux), self._stack(uy, duy), dt, a, b, steps), ux.shape)
+
+    def project_pair(self, ux, uy, dux, duy):
+        return self._split(*self.project(self._stack(ux, dux), self._stack(uy, duy)), ux.shape)
 
     # ---- reverse mode (fvm_autograd.py)
     def explicit_terms_vjp(self, ux, uy, gx, gy, dt: float):
@@ -417,6 +483,10 @@ class PressureProjection(nn.Module):
 
     def forward(self, v):
         ux, uy = _as_pair(v)
+        duals = _unpack_duals(ux, uy)
+        if duals is not None:   # forward mode: the projection is linear, so the stacked pair runs through it as it is
+            (ux, uy), (dux, duy) = _jvp_pairs(*duals, self.grid.shape[0], "pressure_projection")
+            return _make_duals(*self._plan(ux.dtype, ux.device).project_pair(ux, uy, dux, duy))
         plan = self._plan(ux.dtype, ux.device)
         if _ad.wants_grad(ux, uy):
             return _ad.ProjectFn.apply(plan, ux, uy)
@@ -453,6 +523,8 @@ class NavierStokes2DFVMProjection(nn.Module):
         self._projection = PressureProjection(grid=grid)
         self._plans: Dict[tuple, _FvmPlan] = {}
         self._convect_plans: Dict[tuple, _FvmPlan] = {}
+        self._tangent_plans: Dict[tuple, _FvmPlan] = {}           # the tangent variants of the two: plain calls never see them
+        self._convect_tangent_plans: Dict[tuple, _FvmPlan] = {}
 
     def _force_tables(self):
         """(fx, fy) / density at the staggered offsets, sampled once per plan (the forcing is state independent)."""
@@ -467,42 +539,73 @@ class NavierStokes2DFVMProjection(nn.Module):
         return (torch.device(device), dtype, self.grid.shape[0], float(self.viscosity), float(self.density), float(self.drag),
                 fkey, id(inv), inv._version, self.advection.scheme)
 
-    def _plan(self, dtype, device) -> _FvmPlan:
+    def _plan(self, dtype, device, tangent: bool = False) -> _FvmPlan:
         key = self._plan_key(dtype, device)
-        plan = self._plans.get(key)
+        plans = self._tangent_plans if tangent else self._plans
+        plan = plans.get(key)
         if plan is None:
-            self._plans.clear()
+            plans.clear()
             plan = _FvmPlan(self.grid.shape[0], dtype, device, _square_step(self.grid), self.viscosity / self.density,
-                            self.drag, self._projection.solver.inverse, self._force_tables(), self.advection.scheme)
-            self._plans[key] = plan
+                            self.drag, self._projection.solver.inverse, self._force_tables(), self.advection.scheme,
+                            tangent=tangent)
+            plans[key] = plan
         return plan
 
-    def _convect_plan(self, dtype, device) -> _FvmPlan:
+    def _convect_plan(self, dtype, device, tangent: bool = False) -> _FvmPlan:
         """The plan of the advection term alone: no viscosity, no drag, no forcing.  A second full plan, created at the first
         ``convect`` call: it uploads the inverse-eigenvalue table again and owns a transform plan it never runs, and a
         differentiable call holds it until its backward (the autograd node keeps the reference, so clearing the cache
         below is safe)."""
         inv = self._projection.solver.inverse
         key = (torch.device(device), dtype, self.grid.shape[0], id(inv), inv._version, self.advection.scheme)
-        plan = self._convect_plans.get(key)
+        plans = self._convect_tangent_plans if tangent else self._convect_plans
+        plan = plans.get(key)
         if plan is None:
-            self._convect_plans.clear()
+            plans.clear()
             plan = _FvmPlan(self.grid.shape[0], dtype, device, _square_step(self.grid), 0.0, 0.0, inv, None,
-                            self.advection.scheme)
-            self._convect_plans[key] = plan
+                            self.advection.scheme, tangent=tangent)
+            plans[key] = plan
         return plan
 
     def convect(self, u, dt: float):
         """The advection term ``-(u . grad) u`` of the equation's scheme as a pair ``(ux, uy)`` (the reference's
         ``self.convect(v, dt)``): the explicit-terms kernel on a plan without viscosity, drag and forcing."""
         ux, uy = _as_pair(u)
+        duals = _unpack_duals(ux, uy)
+        if duals is not None:   # forward mode: the tangent variant of the advection-only plan
+            (ux, uy), (dux, duy) = _jvp_pairs(*duals, self.grid.shape[0], "convect")
+            return _make_duals(*self._convect_plan(ux.dtype, ux.device, tangent=True).explicit_terms_pair(ux, uy, dux, duy, dt))
         plan = self._convect_plan(ux.dtype, ux.device)
         if _ad.wants_grad(ux, uy):
             return _ad.ExplicitTermsFn.apply(plan, dt, ux, uy)
         return plan.explicit_terms(ux, uy, dt)
 
+    # -- forward mode: the tangent-linear model on the tangent stage kernel (a tangent plan, tcfd_fvm_plan_set_tangent)
+    def explicit_terms_jvp(self, u, du, dt: float):
+        """``((kx, ky), (dkx, dky))``: the explicit terms ``F(u)`` and their directional derivative ``J_F(u) du`` along the
+        pair ``du`` (shapes and dtype of ``u``), one fused launch.  The tangent carries no forcing."""
+        (ux, uy), (dux, duy) = _jvp_pairs(u, du, self.grid.shape[0], "explicit_terms_jvp")
+        return self._plan(ux.dtype, ux.device, tangent=True).explicit_terms_pair(ux, uy, dux, duy, dt)
+
+    def _tangent_steps(self, u, du, dt: float, steps: int, solver: Optional[RKStepper]):
+        if solver is None:
+            raise ValueError("NavierStokes2DFVMProjection: no RKStepper (pass solver=RKStepper.from_method(...))")
+        (ux, uy), (dux, duy) = _jvp_pairs(u, du, self.grid.shape[0], "tangent_step")
+        solver._check_no_grad()
+        a, b = solver.weights(dt)
+        return self._plan(ux.dtype, ux.device, tangent=True).step_pair(ux, uy, dux, duy, dt, a, b, steps)
+
+    def tangent_step(self, u, du, dt: float, steps: int = 1):
+        """``steps`` steps of the equation's solver on the state AND on a perturbation of it: returns
+        ``((ux, uy), (dux, duy))`` with ``du_new = d(u_new)/d(u) . du`` (the tangent-linear model), all stages and
+        projections of all steps in one library call.  ``(n, n)`` or ``(B, n, n)`` components."""
+        return self._tangent_steps(u, du, dt, steps, self.solver)
+
     def explicit_terms(self, u, dt: float):
         ux, uy = _as_pair(u)
+        duals = _unpack_duals(ux, uy)
+        if duals is not None:
+            return _make_duals(*self.explicit_terms_jvp(*duals, dt))
         plan = self._plan(ux.dtype, ux.device)
         if _ad.wants_grad(ux, uy):
             return _ad.ExplicitTermsFn.apply(plan, dt, ux, uy)
@@ -515,8 +618,11 @@ class NavierStokes2DFVMProjection(nn.Module):
         solver = self.solver if solver is None else solver
         if solver is None:
             raise ValueError("NavierStokes2DFVMProjection: no RKStepper (pass solver=RKStepper.from_method(...))")
-        solver._check_no_grad()
         ux, uy = _as_pair(u)
+        duals = _unpack_duals(ux, uy)
+        if duals is not None:   # forward-mode dual numbers: the tangent-linear step carries them
+            return _make_duals(*self._tangent_steps(*duals, dt, steps, solver))
+        solver._check_no_grad()
         a, b = solver.weights(dt)
         plan = self._plan(ux.dtype, ux.device)
         if _ad.wants_grad(ux, uy):
