@@ -14,7 +14,10 @@ columns twice, the r2c transform once).  Nothing here touches torch.fft or the C
 their vector-Jacobian product run on the fused kernels (``FusedExplicitTerms``: 3 launches forward, ~10 backward), and with
 constant coefficients the Runge-Kutta / Crank-Nicolson bookkeeping of a stage is one launch each way as well
 (``StageUpdate``); the tensor-op stage loops below remain for trainable coefficients (whose gradients they produce), for the
-composite grids and as the cross-check (``TCFD_FUSED_STAGE=0``, ``TCFD_FUSED_VJP=0``).
+composite grids and as the cross-check (``TCFD_FUSED_STAGE=0``, ``TCFD_FUSED_VJP=0``).  With constant coefficients, a stepper of
+the package and a fused grid size, ALL stages of all steps are one node (``FusedSteps``): the fused forward step per step, each
+step's input kept, and one ``tcfd_ns2d_step_vjp`` call backward; the per-stage nodes remain as ``TCFD_FUSED_ADJOINT=0`` and as
+the restatement the node differentiates under ``create_graph=True``.
 """
 from __future__ import annotations
 
@@ -257,6 +260,101 @@ def fused_scheduled_steps(op, plan, w_hat, steps, sched, forcing_hat):
             coef = (float(fa[k]), float(sched["beta"][k]), float(sched["gdt"][k]), float(sched["mu"][k]), float(mu_den[k]))
             h, u = StageUpdate.apply(f, h, b, lin, coef)
     return u
+
+
+def _fused_adjoint_ok(plan) -> bool:
+    import os
+
+    return (hasattr(plan, "step_vjp") and hasattr(plan.lib, "tcfd_ns2d_step_vjp")
+            and os.environ.get("TCFD_FUSED_ADJOINT", "1") != "0")
+
+
+def _step_into(plan, src, dst, sched):
+    """One fused step ``src -> dst`` (both (B, n, m) contiguous): THE call every saved state of the adjoint model comes from,
+    in the forward and when a segment is refilled from its checkpoint, so that both give the same bits."""
+    plan.step(src, sched["beta"], sched["gdt"], sched["mu"], 1, 1.0, False, fa=sched.get("fa"), mu_den=sched.get("mu_den"),
+              base0=sched.get("base0"), out=dst)
+
+
+def _step_vjp(op, plan, saved, g, sched, out=None):
+    pre, post = FusedExplicitTerms._tables(op, plan, g.device)
+    return plan.step_vjp(saved, g, pre, post, sched["beta"], sched["gdt"], sched["mu"], fa=sched.get("fa"),
+                         mu_den=sched.get("mu_den"), base0=sched.get("base0"), out=out)
+
+
+def fused_steps_and_adjoint(op, plan, w, g, sched, steps, every=1):
+    """``(w_new, wbar)`` of ``steps`` fused steps from ``w`` (B, n, m) and the cotangent ``g`` of their result, without
+    autograd: the fused forward step once per step into the saved buffer, then ``tcfd_ns2d_step_vjp``.  ``every = c > 1`` keeps
+    only the input of every c-th step and refills one segment of c saved states at a time from its checkpoint."""
+    B = w.shape[0]
+    w_new = torch.empty_like(w)
+    if every <= 1 or steps <= 1:
+        saved = torch.empty((steps,) + tuple(w.shape), dtype=w.dtype, device=w.device)
+        saved[0].copy_(w)
+        for s in range(steps):
+            _step_into(plan, saved[s], saved[s + 1] if s + 1 < steps else w_new, sched)
+        return w_new, _step_vjp(op, plan, saved, g, sched)
+    every = min(every, steps)
+    nseg = (steps + every - 1) // every
+    ckpt = torch.empty((nseg,) + tuple(w.shape), dtype=w.dtype, device=w.device)
+    seg = torch.empty((every,) + tuple(w.shape), dtype=w.dtype, device=w.device)     # also the forward's running states
+    ckpt[0].copy_(w)
+    for s in range(steps):
+        src = ckpt[s // every] if s % every == 0 else seg[s % every]
+        nxt = s + 1
+        dst = w_new if nxt == steps else (ckpt[nxt // every] if nxt % every == 0 else seg[nxt % every])
+        _step_into(plan, src, dst, sched)
+    wbar = g.contiguous().clone()
+    for j in range(nseg - 1, -1, -1):
+        length = min(every, steps - j * every)
+        seg[0].copy_(ckpt[j])
+        for i in range(1, length):
+            _step_into(plan, seg[i - 1], seg[i], sched)
+        _step_vjp(op, plan, seg[:length], wbar, sched, out=wbar)      # in place: g_in may alias g_out
+    return w_new, wbar
+
+
+class FusedSteps(torch.autograd.Function):
+    """All stages of all steps as ONE node when only the state requires grad: the forward is the fused step kernels (one call
+    per step, each step's input kept), the backward one ``tcfd_ns2d_step_vjp`` call that recomputes the stage states -- ``steps``
+    saved fields instead of ``nstages x steps``, and per reversed stage 2 element-wise launches around the explicit terms'
+    adjoint sweep instead of the ~11 of the node chain (``fused_scheduled_steps``)."""
+
+    @staticmethod
+    def forward(ctx, w_hat, op, plan, sched, steps):
+        ctx.op, ctx.plan, ctx.sched, ctx.steps = op, plan, sched, steps
+        w = w_hat.detach().contiguous()
+        if w.numel() == 0:                    # empty batch: empty results both ways, no launch
+            ctx.empty = True
+            return torch.empty_like(w)
+        ctx.empty = False
+        saved = torch.empty((steps,) + tuple(w.shape), dtype=w.dtype, device=w.device)
+        saved[0].copy_(w)
+        out = torch.empty_like(w)
+        for s in range(steps):
+            _step_into(plan, saved[s], saved[s + 1] if s + 1 < steps else out, sched)
+        # the input for the differentiable restatement (create_graph=True), the step inputs for the adjoint model: both through
+        # save_for_backward, so that a backward that does not retain the graph releases the buffer
+        ctx.save_for_backward(w_hat, saved)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.empty:
+            return torch.zeros_like(g), None, None, None, None
+        w_hat, states = ctx.saved_tensors
+        if torch.is_grad_enabled():
+            # create_graph=True: the raw-pointer call below would cut the gradient's own dependence on w and g out of the
+            # graph.  Restate the segment on the per-stage nodes from the saved input and differentiate that (they in turn
+            # restate themselves as tensor ops, see FusedExplicitTerms.backward).
+            del states
+            with torch.enable_grad():
+                w = w_hat if w_hat.requires_grad else w_hat.detach().requires_grad_(True)
+                # (the forcing goes along: the tensor-op explicit terms of TCFD_FUSED_VJP=0 add it themselves)
+                out = fused_scheduled_steps(ctx.op, ctx.plan, w, ctx.steps, ctx.sched, ctx.op._forcing_on(w))
+                (wbar,) = torch.autograd.grad(out, w, g.reshape(out.shape), create_graph=True)
+            return wbar, None, None, None, None
+        return _step_vjp(ctx.op, ctx.plan, states, g.reshape(states.shape[1:]), ctx.sched), None, None, None, None
 
 
 def scheduled_steps(op, plan, w_hat, steps, sched, forcing_hat):

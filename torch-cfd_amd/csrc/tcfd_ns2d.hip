@@ -1,4 +1,4 @@
-// tcfd_ns2d.hip -- the C ABI of the batched 2-D pseudo-spectral vorticity solver (include/tcfd.h): the library's error state,
+// tcfd_ns2d.hip -- the C ABI of the batched 2-D pseudo-spectral vorticity solver (include/tcfd.h, tcfd_ns2d_adjoint.h): the library's error state,
 // plans, argument checks and batch chunking, and the kernels that do not depend on the grid size.  The size-templated kernels
 // live in tcfd_ns2d_sized.hip, built once per precision; an entry point here checks its arguments, cuts the batch into chunks
 // and calls the sized unit of the plan's precision through the ns2d:: templates of tcfd_ns2d_plan.hpp.
@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "tcfd_ns2d_plan.hpp"
+#include "../../include/tcfd_ns2d_adjoint.h"
 
 using namespace tcfd;
 
@@ -469,6 +470,50 @@ extern "C" int tcfd_ns2d_step_jvp(const tcfd_ns2d_plan* p, const void* w_in, con
     return 0;
 }
 
+// ------------------------------------------------------------------ adjoint model (reverse of the fused step)
+// Chunks as the plain step's (the sweeps of a reversed stage are the forward sweep and the explicit terms' VJP, whose working
+// sets are the step's); 12 + nstages chunk-sized fields (VjpWs).
+extern "C" size_t tcfd_ns2d_step_vjp_workspace_bytes(const tcfd_ns2d_plan* p, long batch, int nstages) {
+    if (!p || batch <= 0 || nstages <= 0 || nstages > VJP_MAX_STAGES) return 0;
+    return (size_t)vjp_fields(nstages) * field_bytes(p, chunk_fields(p, batch));
+}
+
+extern "C" int tcfd_ns2d_step_vjp(const tcfd_ns2d_plan* p, const void* saved, const void* g_out, const void* pre, const void* post,
+                                  void* g_in, long batch, int nstages, const double* fa, const double* beta, const double* gdt,
+                                  const double* mu_num, const double* mu_den, const int* base0, int steps, void* ws,
+                                  size_t ws_bytes, void* stream) {
+    if (!p || !saved || !g_out || !pre || !post || !g_in || !beta || !gdt || !mu_num)
+        return fail(TCFD_EINVAL, "step_vjp: null argument");
+    if (batch <= 0) return fail(TCFD_EINVAL, "step_vjp: batch must be > 0");
+    if (steps <= 0) return fail(TCFD_EINVAL, "step_vjp: steps must be > 0 (got %d)", steps);
+    if (nstages <= 0 || nstages > VJP_MAX_STAGES)
+        return fail(TCFD_EINVAL, "step_vjp: nstages %d out of range [1, %d]", nstages, VJP_MAX_STAGES);
+    // (a short workspace is TCFD_EWORKSPACE, as for every call that takes one: include/tcfd.h, Conventions)
+    if (int rc = check_ws(p, batch, ws, ws_bytes, tcfd_ns2d_step_vjp_workspace_bytes(p, batch, nstages))) return rc;
+    const size_t esz = (p->dtype == TCFD_C128 ? 16 : 8) * (size_t)p->n * p->m;      // bytes of one field, caller layout
+    {
+        const unsigned char *s0 = (const unsigned char*)saved, *s1 = s0 + (size_t)steps * batch * esz;
+        const unsigned char *g0 = (const unsigned char*)g_in, *g1 = g0 + (size_t)batch * esz;
+        if (g0 < s1 && s0 < g1) return fail(TCFD_EINVAL, "step_vjp: g_in overlaps saved (the saved states are read to the end)");
+        // g_in == g_out is in place (every chunk reads its own part of g_out first); a shifted overlap would let a later chunk read
+        // what an earlier one wrote
+        const unsigned char* o0 = (const unsigned char*)g_out;
+        if (g0 != o0 && g0 < o0 + (size_t)batch * esz && o0 < g1)
+            return fail(TCFD_EINVAL, "step_vjp: g_in overlaps g_out without being g_out (identical or disjoint)");
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const size_t step_stride = (size_t)batch * p->n * p->m;      // elements between saved[s] and saved[s + 1]
+    const long chunk = chunk_fields(p, batch);
+    for (long b0 = 0; b0 < batch; b0 += chunk) {
+        const long nb = std::min(chunk, batch - b0);
+        const size_t o = (size_t)b0 * esz;
+        int rc = NS2D_SIZED(p, step_vjp, p, (const unsigned char*)saved + o, step_stride, (const unsigned char*)g_out + o, pre, post,
+                            (unsigned char*)g_in + o, nb, nstages, fa, beta, gdt, mu_num, mu_den, base0, steps, ws, st);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
 extern "C" int tcfd_ns2d_stream_residual(const tcfd_ns2d_plan* p, const void* w, const void* wt, void* psi,
                                          void* residual, long batch, void* ws, size_t ws_bytes, void* stream) {
     if (!p || !w || batch <= 0 || (residual && !wt)) return fail(TCFD_EINVAL, "stream_residual: bad argument");
@@ -733,21 +778,7 @@ extern "C" int tcfd_host_unregister(void* ptr) {
 // plain one to round-off.  autograd.py ran this as ~10 element-wise tensor launches forward and ~20 backward per stage; these
 // two kernels are the stage and its vector-Jacobian product in one launch each:
 //     G = g_h + gdt r (.) g_u ,   g_f = fa G ,   g_hprev = beta G ,   g_b = (1 + mu L) r (.) g_u ,      r = 1 / (1 - mud L).
-template <typename T>
-__global__ __launch_bounds__(256) void k_stage_update(const cx<T>* __restrict__ f, const cx<T>* __restrict__ hp,
-                                                      const cx<T>* __restrict__ b, const T* __restrict__ Lt, T fa, T beta, T gdt,
-                                                      T mu, T mud, cx<T>* __restrict__ h, cx<T>* __restrict__ u, long total,
-                                                      long plane) {
-    for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256L) {
-        const T L = Lt[e % plane];
-        cx<T> hn = cscale(f[e], fa);
-        if (hp) hn = hn + cscale(hp[e], beta);
-        const cx<T> bv = b[e];
-        const cx<T> rhs = bv + cscale(hn, gdt) + cscale(cscale(bv, L), mu);
-        h[e] = hn;
-        u[e] = cscale(rhs, fast_rcp((T)1 - mud * L));
-    }
-}
+// (k_stage_update: tcfd_ns2d_plan.hpp -- the recomputation of tcfd_ns2d_step_vjp in the sized units launches it too.)
 template <typename T>
 __global__ __launch_bounds__(256) void k_stage_update_vjp(const cx<T>* __restrict__ gu, const cx<T>* __restrict__ gh,
                                                           const T* __restrict__ Lt, T fa, T beta, T gdt, T mu, T mud,

@@ -192,6 +192,60 @@ static JvpWs<T> carve_jvp(const tcfd_ns2d_plan* p, void* ws, long batch) {
     return w;
 }
 
+// Scratch of the adjoint model (tcfd_ns2d_step_vjp): the 8 fields of `Ws` for the forward and the adjoint sweeps of the explicit
+// terms (which touch `adv` and `planes` only), with the three fields those sweeps leave alone put to use, then 4 fields of X_f,
+// the cotangent of the step's initial state and the recomputed stage states u_1 .. u_{nstages-1}: 12 + nstages fields.
+constexpr int VJP_MAX_STAGES = 32;
+static inline int vjp_fields(int nstages) { return 12 + nstages; }
+template <typename T>
+struct VjpWs {
+    cx<T>* ubar;          // Ws::h: the running cotangent of the state, alive from one reversed step to the next
+    cx<T>* F;             // plane 0 of Ws::planes: F(u_k) of the recomputation (the planes are dead after the row pass)
+    cx<T>* hf[2];         // Ws::upad, Ws::upad2: the accumulator h of the recomputation, ping-pong ...
+    cx<T>* gm;            // ... then (same fields, the recomputation is over) the pre-weighted cotangent of F
+    cx<T>* hbar;          //     and the cotangent of h
+    cx<T>* X;             // the four half spectra of explicit_vjp, `stride` apart
+    cx<T>* ustart;        // cotangent of the step's initial state through the base0 stages
+    cx<T>* u;             // u_1 .. u_{nstages-1}, `stride` apart
+    size_t stride;        // elements per field
+};
+template <typename T>
+static VjpWs<T> carve_vjp(const tcfd_ns2d_plan* p, void* ws, long batch) {
+    const size_t fb = field_bytes(p, batch);
+    unsigned char* base = (unsigned char*)ws;
+    auto at = [&](int i) { return (cx<T>*)(base + (size_t)i * fb); };
+    VjpWs<T> w;
+    w.ubar = at(0);
+    w.F = at(2);
+    w.hf[0] = w.gm = at(6);
+    w.hf[1] = w.hbar = at(7);
+    w.X = at(8);
+    w.ustart = at(12);
+    w.u = at(13);
+    w.stride = fb / sizeof(cx<T>);
+    return w;
+}
+
+// One stage of the schedule with constant coefficients, written exactly as the fused forward kernels write it (k_cols, MODE_C):
+//     h = fa f + beta h_prev ,    u = (b + gdt h + mu L b) / (1 - mud L)            (L: the real (n, m) linear term)
+// Launched by tcfd_ns2d_stage_update (the differentiable step of autograd.py) and by the recomputation of tcfd_ns2d_step_vjp.
+template <typename T>
+__global__ __launch_bounds__(256) void k_stage_update(const cx<T>* __restrict__ f, const cx<T>* __restrict__ hp,
+                                                      const cx<T>* __restrict__ b, const T* __restrict__ Lt, T fa, T beta, T gdt,
+                                                      T mu, T mud, cx<T>* __restrict__ h, cx<T>* __restrict__ u, long total,
+                                                      long plane) {
+    using namespace tcfd;
+    for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256L) {
+        const T L = Lt[e % plane];
+        cx<T> hn = cscale(f[e], fa);
+        if (hp) hn = hn + cscale(hp[e], beta);
+        const cx<T> bv = b[e];
+        const cx<T> rhs = bv + cscale(hn, gdt) + cscale(cscale(bv, L), mu);
+        h[e] = hn;
+        u[e] = cscale(rhs, fast_rcp((T)1 - mud * L));
+    }
+}
+
 // Largest batch of one call: the launch grids and the block -> tile maps of the column kernels (ColArgs::batch, ntiles) are
 // 32-bit.  A column grid is at most 2 (parities) x (batch x tiles rounded up to 8 line groups) <= batch (2 m + 16) workgroups
 // with one-column tiles, a row grid batch n / 2: batch (n + 18) < 2^31 keeps every one of them, and every product of two of
@@ -232,6 +286,11 @@ template <typename T>
 int step_jvp(const tcfd_ns2d_plan* p, const void* w_in, const void* dw_in, void* w_out, void* dw_out, long batch, int nstages,
              const double* fa, const double* beta, const double* gdt, const double* mu_num, const double* mu_den,
              const int* base0, int steps, void* ws, hipStream_t st);
+// one chunk of tcfd_ns2d_step_vjp; saved_step_stride: elements between the saved inputs of two consecutive steps
+template <typename T>
+int step_vjp(const tcfd_ns2d_plan* p, const void* saved, size_t saved_step_stride, const void* g_out, const void* pre,
+             const void* post, void* g_in, long batch, int nstages, const double* fa, const double* beta, const double* gdt,
+             const double* mu_num, const double* mu_den, const int* base0, int steps, void* ws, hipStream_t st);
 template <typename T> int rfft2(const tcfd_ns2d_plan* p, const void* x, void* out, long batch, hipStream_t st);
 template <typename T> int irfft2(const tcfd_ns2d_plan* p, const void* xh, void* out, long batch, void* ws, hipStream_t st);
 template <typename T> int irfft2_sub_max(const tcfd_ns2d_plan* p);

@@ -2058,6 +2058,104 @@ static int step_jvp_impl(const tcfd_ns2d_plan* p, const void* w_in, const void* 
     return 0;
 }
 
+// ------------------------------------------------------------------ adjoint model (reverse of the fused step)
+// Reverse of stage k of the schedule, everything that is element-wise (the transposes of k_stage_update, of the `g * pre`
+// weighting and of the additions autograd performs between its nodes), one launch:
+//     g = r (.) ubar_{k+1} ,  G = hbar_k + gdt g ,  gm = pre (.) fa G ,  hbar_{k-1} = beta G ,  bbar = (1 + mu L) g ,  r = 1 / (1 - mud L)
+// ub / hb null: a zero cotangent (hbar is zero at the last stage of every step).  hprev null: first stage, nobody reads it.  bbar
+// is the cotangent of the stage's base state: of u_k (-> acc, which the closing kernel completes to ubar_k), or, when `ustart` is
+// given (a base0 stage), of the step's initial state (-> ustart, stored or added; acc = 0).  acc may be ub and hprev may be hb
+// (every element is read before it is written, by the same thread) -- hence no __restrict__ on them.
+template <typename T>
+__global__ __launch_bounds__(256) void k_stage_adjoint(const cx<T>* ub, const cx<T>* hb, const T* __restrict__ Lt,
+                                                       const T* __restrict__ pre, T fa, T beta, T gdt, T mu, T mud,
+                                                       cx<T>* __restrict__ gm, cx<T>* hprev, cx<T>* acc, cx<T>* ustart,
+                                                       int ustart_add, long total, long plane) {
+    for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256L) {
+        const long t = e % plane;
+        const T L = Lt[t];
+        cx<T> g = mk<T>((T)0, (T)0);
+        if (ub) g = cscale(ub[e], fast_rcp((T)1 - mud * L));
+        cx<T> G = cscale(g, gdt);
+        if (hb) G = G + hb[e];
+        gm[e] = cscale(cscale(G, fa), pre[t]);
+        if (hprev) hprev[e] = cscale(G, beta);
+        const cx<T> bb = g + cscale(cscale(g, L), mu);
+        if (ustart) {
+            ustart[e] = ustart_add ? ustart[e] + bb : bb;
+            acc[e] = mk<T>((T)0, (T)0);
+        } else {
+            acc[e] = bb;
+        }
+    }
+}
+
+// ubar_k = acc + sum_f post_f (.) X_f [+ extra]: the closing sum of the explicit terms' vector-Jacobian product (k_vjp_combine's
+// arithmetic) and the accumulation into the stage's cotangent in one pass.  out may be acc.
+template <typename T>
+__global__ __launch_bounds__(256) void k_vjp_close(const cx<T>* acc, const cx<T>* __restrict__ extra, const cx<T>* __restrict__ X,
+                                                   size_t x_stride, const cx<T>* __restrict__ post, cx<T>* out, long total,
+                                                   long plane) {
+    for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256L) {
+        const long t = e % plane;
+        cx<T> s = mk<T>((T)0, (T)0);
+#pragma unroll
+        for (int f = 0; f < 4; ++f) {
+            const cx<T> x = X[(size_t)f * x_stride + e], q = post[(long)f * plane + t];
+            s = s + mk<T>(x.x * q.x - x.y * q.y, x.x * q.y + x.y * q.x);
+        }
+        s = acc[e] + s;
+        if (extra) s = s + extra[e];
+        out[e] = s;
+    }
+}
+
+// `steps` steps of the schedule of tcfd_ns2d_step_imex in reverse, last step first, for one chunk.  Per step: the stage states
+// u_1 .. u_{nstages-1} are recomputed from the step's saved input (explicit_impl + k_stage_update, 4 launches per stage), then
+// the stages are reversed: k_stage_adjoint, the adjoint sweep of the explicit terms at u_k (explicit_vjp_impl), k_vjp_close.
+template <typename T, int N>
+static int step_vjp_impl(const tcfd_ns2d_plan* p, const void* saved, size_t saved_step_stride, const void* g_out, const void* pre,
+                         const void* post, void* g_in, long batch, int nstages, const double* fa, const double* beta,
+                         const double* gdt, const double* mu, const double* mud, const int* base0, int steps, void* ws,
+                         hipStream_t st) {
+    VjpWs<T> V = carve_vjp<T>(p, ws, batch);
+    const long plane = (long)N * p->m, total = batch * plane;
+    const unsigned blocks = (unsigned)std::min<long>((total + 255) / 256, 1 << 16);
+    const T* lin = (const T*)p->lin;
+    auto c = [&](const double* v, int k, double dflt) { return v ? (T)v[k] : (T)dflt; };
+    const cx<T>* ub = (const cx<T>*)g_out;
+    int rc;
+    for (int s = steps - 1; s >= 0; --s) {
+        const cx<T>* u0 = (const cx<T>*)saved + (size_t)s * saved_step_stride;
+        auto state = [&](int k) { return k == 0 ? u0 : (const cx<T>*)(V.u + (size_t)(k - 1) * V.stride); };
+        auto from_u0 = [&](int k) { return k > 0 && base0 && base0[k]; };    // (at k = 0 the initial state IS the current one)
+        for (int k = 0; k + 1 < nstages; ++k) {
+            if ((rc = explicit_impl<T, N>(p, state(k), V.F, nullptr, nullptr, false, batch, ws, st))) return rc;
+            hipLaunchKernelGGL(k_stage_update<T>, dim3(blocks), dim3(256), 0, st, (const cx<T>*)V.F,
+                               k ? (const cx<T>*)V.hf[(k - 1) & 1] : nullptr, from_u0(k) ? u0 : state(k), lin, c(fa, k, 1),
+                               (T)beta[k], (T)gdt[k], (T)mu[k], c(mud, k, mu[k]), V.hf[k & 1],
+                               V.u + (size_t)k * V.stride, total, plane);
+            HIP_TRY(hipGetLastError());
+        }
+        bool ustart_live = false;
+        for (int k = nstages - 1; k >= 0; --k) {
+            hipLaunchKernelGGL(k_stage_adjoint<T>, dim3(blocks), dim3(256), 0, st, ub,
+                               k == nstages - 1 ? nullptr : (const cx<T>*)V.hbar, lin, (const T*)pre, c(fa, k, 1), (T)beta[k],
+                               (T)gdt[k], (T)mu[k], c(mud, k, mu[k]), V.gm, k ? V.hbar : nullptr, V.ubar,
+                               from_u0(k) ? V.ustart : nullptr, ustart_live ? 1 : 0, total, plane);
+            HIP_TRY(hipGetLastError());
+            ustart_live |= from_u0(k);
+            ub = V.ubar;
+            if ((rc = explicit_vjp_impl<T, N>(p, state(k), V.gm, V.X, V.stride, batch, ws, st))) return rc;
+            hipLaunchKernelGGL(k_vjp_close<T>, dim3(blocks), dim3(256), 0, st, (const cx<T>*)V.ubar,
+                               (k == 0 && ustart_live) ? (const cx<T>*)V.ustart : nullptr, (const cx<T>*)V.X, V.stride,
+                               (const cx<T>*)post, (s == 0 && k == 0) ? (cx<T>*)g_in : V.ubar, total, plane);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    return 0;
+}
+
 template <typename T, int N>
 static int irfft2_sub_max_impl(const tcfd_ns2d_plan*) {
     using Gm = RowGeom<T, N, Cfg<T, N>::ROW_EPT>;
@@ -2129,6 +2227,15 @@ int step_jvp(const tcfd_ns2d_plan* p, const void* w_in, const void* dw_in, void*
     });
 }
 template <typename T>
+int step_vjp(const tcfd_ns2d_plan* p, const void* saved, size_t saved_step_stride, const void* g_out, const void* pre,
+             const void* post, void* g_in, long batch, int nstages, const double* fa, const double* beta, const double* gdt,
+             const double* mu_num, const double* mu_den, const int* base0, int steps, void* ws, hipStream_t st) {
+    return by_size(p->n, [&](auto N) {
+        return step_vjp_impl<T, N()>(p, saved, saved_step_stride, g_out, pre, post, g_in, batch, nstages, fa, beta, gdt, mu_num,
+                                     mu_den, base0, steps, ws, st);
+    });
+}
+template <typename T>
 int rfft2(const tcfd_ns2d_plan* p, const void* x, void* out, long batch, hipStream_t st) {
     return by_size(p->n, [&](auto N) { return rfft2_impl<T, N()>(p, x, out, batch, st); });
 }
@@ -2156,6 +2263,7 @@ template decltype(explicit_terms<TCFD_REAL>) explicit_terms<TCFD_REAL>;
 template decltype(explicit_vjp<TCFD_REAL>) explicit_vjp<TCFD_REAL>;
 template decltype(explicit_jvp<TCFD_REAL>) explicit_jvp<TCFD_REAL>;
 template decltype(step_jvp<TCFD_REAL>) step_jvp<TCFD_REAL>;
+template decltype(step_vjp<TCFD_REAL>) step_vjp<TCFD_REAL>;
 template decltype(rfft2<TCFD_REAL>) rfft2<TCFD_REAL>;
 template decltype(irfft2<TCFD_REAL>) irfft2<TCFD_REAL>;
 template decltype(irfft2_sub_max<TCFD_REAL>) irfft2_sub_max<TCFD_REAL>;

@@ -18,7 +18,9 @@ n = p * 2^k with a small odd p (48, 112, 224, ...: power-of-two HIP transforms +
 -- anything else raises.  The fused kernels are
 forward-only; when gradients are asked for (a state that requires grad, trainable
 stepper coefficients) the operator steps through ``autograd.py``: the same arithmetic
-as device tensor ops around the HIP transforms and their hand-written adjoints.  A forward-mode dual number
+as device tensor ops around the HIP transforms and their hand-written adjoints -- or, when only the state requires grad, one
+node whose backward is the adjoint model of the fused step (``tcfd_ns2d_step_vjp``; ``adjoint_step`` is the same without
+autograd).  A forward-mode dual number
 (``torch.autograd.forward_ad``) as the state runs the tangent-linear kernels (``explicit_terms_jvp`` / ``tangent_step``).
 """
 from __future__ import annotations
@@ -131,11 +133,16 @@ class _HipPlan:
 
     # -- operations
     def step(self, w, beta, gdt, mu, steps: int, inv_total_dt: float, want_dwdt: bool = True, fa=None, mu_den=None,
-             base0=None):
+             base0=None, out=None):
         """``steps`` fused IMEX steps; stage k: h <- fa_k F(u) + beta_k h, u <- (base + gdt_k h + mu_k L base) / (1 - mu_den_k L)
-        (include/tcfd.h, tcfd_ns2d_step_imex).  fa / mu_den / base0 default to the RK4-CN form (1, mu, current state)."""
+        (include/tcfd.h, tcfd_ns2d_step_imex).  fa / mu_den / base0 default to the RK4-CN form (1, mu, current state).
+        ``out``: a contiguous tensor of the state's shape and the plan's dtype to receive the new state (a slot of the adjoint
+        model's saved buffer)."""
         w, batch = self._prep(w)
-        out = torch.empty_like(w)
+        if out is None:
+            out = torch.empty_like(w)
+        elif out.dtype != self.cdtype or out.shape != w.shape or not out.is_contiguous() or out.device != w.device:
+            raise ValueError("step: `out` must be a contiguous tensor of the state's shape, dtype and device")
         dwdt = torch.empty_like(w) if want_dwdt else None
         if batch == 0:   # empty batch: the reference's tensor ops return empty tensors
             return out, dwdt
@@ -218,6 +225,46 @@ class _HipPlan:
                 _lib.darray(mu_den) if mu_den is not None else None, ints, steps, ws.data_ptr(), ws.numel(), self._stream())
         _lib.check(rc, "tcfd_ns2d_step_jvp")
         return out, dout
+
+    def step_vjp_workspace(self, batch: int, nstages: int) -> torch.Tensor:
+        """Scratch of the adjoint model (``tcfd_ns2d_step_vjp_workspace_bytes``): the same buffer as ``workspace``, grown."""
+        if not hasattr(self.lib, "tcfd_ns2d_step_vjp"):   # added without a new ABI number: a stale library loads, but lacks it
+            raise _lib.TcfdError(f"{_lib.LIB_PATH} was built before the adjoint model (tcfd_ns2d_step_vjp) was added: "
+                                 "rebuild it with torch_cfd_amd._lib.build_library(force=True)")
+        need = self.lib.tcfd_ns2d_step_vjp_workspace_bytes(self.handle, batch, nstages)
+        if need == 0:
+            raise _lib.TcfdError(f"tcfd_ns2d_step_vjp_workspace_bytes: batch = {batch}, nstages = {nstages} out of range")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def step_vjp(self, saved, g_out, pre, post, beta, gdt, mu, fa=None, mu_den=None, base0=None, out=None):
+        """Reverse of ``saved.shape[0]`` steps of the schedule of ``step`` (``tcfd_ns2d_step_vjp``): ``saved`` (steps, B, n, m)
+        holds the input of every step, ``g_out`` (B, n, m) the cotangent of the last result; returns the cotangent of
+        ``saved[0]`` (written into ``out`` when given; ``out`` may be ``g_out``).  ``pre`` / ``post``: the tables of
+        ``autograd.FusedExplicitTerms._tables``."""
+        if saved.dim() != 4 or saved.dtype != self.cdtype or not saved.is_contiguous():
+            raise ValueError(f"step_vjp: expected a contiguous (steps, B, {self.n}, {self.m}) {self.cdtype} buffer of saved states")
+        g_out, batch = self._prep(g_out)
+        steps = saved.shape[0]
+        if tuple(saved.shape[1:]) != (batch, self.n, self.m) or g_out.dim() != 3:
+            raise ValueError(f"step_vjp: saved {tuple(saved.shape)} does not match the cotangent {tuple(g_out.shape)}")
+        if out is None:
+            out = torch.empty_like(g_out)
+        elif out.dtype != self.cdtype or out.shape != g_out.shape or not out.is_contiguous():
+            raise ValueError("step_vjp: `out` must be a contiguous tensor of the cotangent's shape and dtype")
+        if batch == 0:
+            return out
+        ws = self.step_vjp_workspace(batch, len(beta))
+        ints = (ctypes.c_int * len(beta))(*[int(v) for v in base0]) if base0 is not None else None
+        with torch.cuda.device(self.device):
+            rc = self.lib.tcfd_ns2d_step_vjp(
+                self.handle, saved.data_ptr(), g_out.data_ptr(), pre.data_ptr(), post.data_ptr(), out.data_ptr(), batch,
+                len(beta), _lib.darray(fa) if fa is not None else None, _lib.darray(beta), _lib.darray(gdt), _lib.darray(mu),
+                _lib.darray(mu_den) if mu_den is not None else None, ints, steps, ws.data_ptr(), ws.numel(), self._stream())
+        _lib.check(rc, "tcfd_ns2d_step_vjp")
+        return out
 
     def stream_residual(self, w, wt, want_psi=True, want_res=True):
         w, batch = self._prep(w)
@@ -625,9 +672,14 @@ class NavierStokes2DSpectral(ImplicitExplicitODE):
         constant = not any(torch.is_tensor(v) and v.requires_grad for v in params.values())
         if (constant and ad._fused_vjp_ok(plan) and _is_module_stepper(stepper) and os.environ.get("TCFD_FUSED_STAGE", "1") != "0"
                 and w.is_cuda):
-            # only the STATE asks for gradients: the schedule is plain numbers (rounded as the fused forward kernels round
-            # them), every stage is two fused nodes -- F(w) with its VJP and the stage update with its VJP
-            out = ad.fused_scheduled_steps(self, plan, w, steps, stepper.stage_schedule(params, dt), forcing)
+            # only the STATE asks for gradients: the schedule is plain numbers (rounded as the fused forward kernels round them)
+            if ad._fused_adjoint_ok(plan) and steps >= 1:
+                # ONE node for all steps: the fused forward step saves every step's input, the backward is one
+                # tcfd_ns2d_step_vjp call (steps saved fields instead of nstages x steps)
+                out = ad.FusedSteps.apply(w, self, plan, stepper.stage_schedule(params, dt), steps)
+            else:
+                # every stage is two fused nodes -- F(w) with its VJP and the stage update with its VJP
+                out = ad.fused_scheduled_steps(self, plan, w, steps, stepper.stage_schedule(params, dt), forcing)
         elif isinstance(stepper, RK4CrankNicolsonStepper):
             out = ad.rk_crank_nicolson_steps(self, plan, w, dt, steps, params, forcing)
         else:   # alpha / beta stay tensors: a trainable IMEX scheme gets its gradients (as the reference's 0-dim arithmetic gives)
@@ -645,10 +697,11 @@ class NavierStokes2DSpectral(ImplicitExplicitODE):
         return self._coef_cache[1]
 
     # -- forward mode: the tangent-linear model on its own kernels (tcfd_ns2d_explicit_terms_jvp / tcfd_ns2d_step_jvp)
-    def _jvp_plan(self, w_hat, dw_hat, what: str) -> _HipPlan:
-        """Checks shared by the tangent-linear entry points, in the order shapes (ValueError) -> gradients -> device plan."""
+    def _jvp_plan(self, w_hat, dw_hat, what: str, dual: str = "tangent", kernels: str = "tangent-linear") -> _HipPlan:
+        """Checks shared by the tangent-linear entry points and the adjoint model (``dual`` = "cotangent"), in the order shapes
+        (ValueError) -> gradients -> device plan."""
         if not (torch.is_tensor(w_hat) and torch.is_tensor(dw_hat)) or w_hat.shape != dw_hat.shape or w_hat.dtype != dw_hat.dtype:
-            raise ValueError(f"{what}: the tangent must have the shape and dtype of the state, got "
+            raise ValueError(f"{what}: the {dual} must have the shape and dtype of the state, got "
                              f"{tuple(getattr(dw_hat, 'shape', ()))} {getattr(dw_hat, 'dtype', None)} for "
                              f"{tuple(getattr(w_hat, 'shape', ()))} {getattr(w_hat, 'dtype', None)}")
         n, m = self.kx.shape[-2:]
@@ -656,11 +709,12 @@ class NavierStokes2DSpectral(ImplicitExplicitODE):
             raise ValueError(f"{what}: expected a complex (n, m), (B, n, m) or (B, T, n, m) half spectrum with (n, m) = "
                              f"({n}, {m}), got {tuple(w_hat.shape)} {w_hat.dtype}")
         if self._wants_grad(w_hat, dw_hat):
-            raise NotImplementedError(f"{what}: forward mode over reverse mode is not implemented -- the state or its tangent "
+            mode = "forward mode over reverse mode" if dual == "tangent" else "reverse mode over the adjoint model"
+            raise NotImplementedError(f"{what}: {mode} is not implemented -- the state or its {dual} "
                                       "requires grad in grad mode; detach them or differentiate with the reverse-mode path alone")
         plan = self._plan(w_hat)
         if not isinstance(plan, _HipPlan):
-            raise NotImplementedError(f"{what}: the tangent-linear kernels cover the fused grid sizes only (n = 2^k in 8..4096, "
+            raise NotImplementedError(f"{what}: the {kernels} kernels cover the fused grid sizes only (n = 2^k in 8..4096, "
                                       f"3 * 2^k in 96..1536, 5 * 2^k in 80..1280); n = {n} runs on the composite / dense plans")
         return plan
 
@@ -689,6 +743,51 @@ class NavierStokes2DSpectral(ImplicitExplicitODE):
         if self.solver is None:
             raise TypeError("NavierStokes2DSpectral needs a solver (e.g. RK4CrankNicolsonStepper()) to step")
         return self._tangent_steps(w_hat, dw_hat, dt, steps, self.solver.params, self.solver)
+
+    # -- reverse mode as an explicit call: the adjoint model on its own kernels (tcfd_ns2d_step_vjp), no autograd involved
+    def adjoint_step(self, w_hat, g_hat, dt, steps=1, g_dwdt=None, checkpoint_every=1) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``steps`` steps of the operator's stepper and their transpose: returns ``(w_new, wbar)`` with ``w_new`` the stepped
+        state and ``wbar = (d w_new / d w)^T g_hat`` the cotangent of ``w_hat`` (the adjoint model; ``<J dw, g> = <dw, wbar>``
+        in the real inner product with ``J dw`` of ``tangent_step``).  ``g_dwdt``: cotangent of the second output of
+        ``forward``, ``(w_new - w) / (steps dt)``, folded in.  The forward runs the fused step once per step and keeps every
+        step's input; the reverse is one library call.  ``checkpoint_every = c`` keeps every c-th input only and refills one
+        segment at a time from its checkpoint with the same fused calls (about ``steps / c + c`` fields instead of ``steps``;
+        the same bits)."""
+        if self.solver is None:
+            raise TypeError("NavierStokes2DSpectral needs a solver (e.g. RK4CrankNicolsonStepper()) to step")
+        steps, c = int(steps), int(checkpoint_every)
+        if steps < 1 or c < 1:
+            raise ValueError(f"adjoint_step: steps and checkpoint_every must be >= 1, got {steps}, {checkpoint_every}")
+        if g_dwdt is not None and (not torch.is_tensor(g_dwdt) or g_dwdt.shape != w_hat.shape or g_dwdt.dtype != w_hat.dtype):
+            raise ValueError("adjoint_step: g_dwdt must have the shape and dtype of the state")
+        plan = self._jvp_plan(w_hat, g_hat, "adjoint_step", dual="cotangent", kernels="adjoint")
+        if self._wants_grad(g_dwdt):
+            raise NotImplementedError("adjoint_step: reverse mode over the adjoint model is not implemented -- g_dwdt requires grad "
+                                      "in grad mode; detach it or differentiate with the reverse-mode path alone")
+        stepper = self.solver
+        if not _is_module_stepper(stepper):
+            raise NotImplementedError("adjoint_step: the fused adjoint model needs a stepper of this module (IMEXStepper, "
+                                      "RK4CrankNicolsonStepper); a foreign solver differentiates through explicit_terms")
+        params = stepper.params
+        if self._wants_grad(*params.values()):
+            raise NotImplementedError("adjoint_step: trainable stepper coefficients (requires_grad=True) are not implemented in the "
+                                      "adjoint model; freeze the coefficients or differentiate forward() with autograd")
+        from . import autograd as ad
+
+        sc = self._schedule(stepper, params, dt)
+        lead = w_hat.shape
+        w = w_hat.detach().to(plan.cdtype).reshape(-1, plan.n, plan.m).contiguous()
+        g = g_hat.detach().to(plan.cdtype).reshape(w.shape)
+        scale = 1.0 / (steps * dt)
+        if g_dwdt is not None:
+            gd = g_dwdt.detach().to(plan.cdtype).reshape(w.shape) * scale
+            g = g + gd
+        if w.shape[0] == 0:
+            return torch.empty_like(w).reshape(lead), torch.empty_like(w).reshape(lead)
+        w_new, wbar = ad.fused_steps_and_adjoint(self, plan, w, g, sc, steps, c)
+        if g_dwdt is not None:
+            wbar = wbar - gd
+        return w_new.reshape(lead), wbar.reshape(lead)
 
     def _fused_steps(self, vort_hat, dt, steps, params=None, want_dwdt=True, stepper=None):
         stepper = self.solver if stepper is None else stepper
