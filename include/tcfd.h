@@ -119,6 +119,25 @@ void tcfd_ns2d_plan_destroy(tcfd_ns2d_plan* plan);
  * accumulator are identically zero outside the 2/3-rule mask so those entries are never stored. */
 int tcfd_ns2d_plan_info(const tcfd_ns2d_plan* plan, int* separable, int* sparse_forcing, int* keep_cols);
 
+/* Per-sample physics: an ENSEMBLE plan.  After this call, field b of every call on the plan (b = its position in the CALLER's batch,
+ * whatever chunks the call is cut into) steps with its own linear term and forcing amplitude,
+ *     L_b = nu[b] * laplace - drag[b]        two rounded operations in the plan's real type, as the tensor arithmetic that forms
+ *                                            the (n, m) table of a scalar plan rounds them
+ *     f_b = forcing_scale[b] * forcing_hat   the forcing spectrum of tcfd_ns2d_plan_create
+ * instead of the linear_term table of tcfd_ns2d_plan_create.  laplace[n*m]: the operator's Laplacian symbol -4 pi^2 (kx^2 + ky^2)
+ * (host, double); nu[count], drag[count] (NULL: 0), forcing_scale[count] (NULL: 1): host arrays, copied -- the plan owns its
+ * count x {nu, drag, forcing_scale} table.  The kernels take the Laplacian as its column 0 and row 0 when every member's L_b
+ * passes the plan's separability test (then member b is stepped with the bits a scalar plan of (nu[b], drag[b]) steps with), as
+ * the dense table otherwise.  Added under revision 13 without a new number, like tcfd_fvm_plan_set_tangent: a plan keeps its
+ * behaviour until this call turns the mode on, count = 0 turns it off again (the plan steps with its own linear_term, the same
+ * bits as before), and a host looks the symbol up.  The call waits for the device and drops the plan's captured graphs.
+ * On an ensemble plan tcfd_ns2d_step, tcfd_ns2d_step_imex, tcfd_ns2d_explicit_terms and tcfd_ns2d_stream_residual require
+ * batch == count (TCFD_EINVAL naming both numbers otherwise); the tangent-linear, adjoint and refiner entry points
+ * (tcfd_ns2d_explicit_terms_jvp, tcfd_ns2d_step_jvp, tcfd_ns2d_explicit_terms_vjp, tcfd_ns2d_step_vjp, tcfd_ns2d_refine,
+ * tcfd_ns2d_refine_vjp) return TCFD_EINVAL: their kernels read one linear-term table. */
+int tcfd_ns2d_plan_set_ensemble(tcfd_ns2d_plan* plan, long count, const double* laplace, const double* nu, const double* drag,
+                                const double* forcing_scale);
+
 /* Which kernel variants the plan launches: split = 1 when the column transform is cut radix-2 across the
  * row pass (default at n = 1024 and n = 4096); rows_kernel = 5 (register staged) or 7 (cross-lane transforms, n = 1024). */
 int tcfd_ns2d_plan_variant(const tcfd_ns2d_plan* plan, int* split, int* rows_kernel);

@@ -89,7 +89,8 @@ def build_library(force: bool = False, verbose: bool = False, only=None) -> str:
 # tcfd_fno_tiles.hip 62 s, tcfd_residual.hip about a minute, tcfd_fvm.hip 4 s -- nowhere near that path, so nothing is gained by
 # splitting them.  build_library(force=True) on an 8-core machine, the 16 jobs of the earlier two-unit split of those three
 # against these 13, two runs each in turn: 189.5 s, 226.1 s (13), 224.4 s, 209.0 s (13) -- the same within the 35 s the 16-job
-# build differs from itself.
+# build differs from itself.  (Per-sample parameters added the ENS = 1 twins of the update / closing column kernels to the two sized
+# units, 200 kernels each: the same 8-core build 249 s -> 304 s, still bound by those two jobs.)
 JOBS = (("tcfd_ns2d_sized.hip", ("-DTCFD_REAL=double",), "tcfd_ns2d_f64.o"),
         ("tcfd_ns2d_sized.hip", ("-DTCFD_REAL=float",), "tcfd_ns2d_f32.o"),
         ("tcfd_ns2d.hip", (), "tcfd_ns2d.o"),
@@ -142,6 +143,7 @@ SIGNATURES = {
     "tcfd_ns2d_plan_create": (_i, [ctypes.POINTER(_vp), _i, _i, _dp, _dp, _dp, _dp, _dp]),
     "tcfd_ns2d_plan_destroy": (None, [_vp]),
     "tcfd_ns2d_plan_info": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "tcfd_ns2d_plan_set_ensemble": (_i, [_vp, _l, _dp, _dp, _dp, _dp]),
     "tcfd_ns2d_plan_variant": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "tcfd_ns2d_plan_chunking": (_i, [_vp, _l, ctypes.POINTER(_l), ctypes.POINTER(_sz), ctypes.POINTER(_i)]),
     "tcfd_debug_xl_fft1024": (_i, [_vp, _vp, _vp, _i, _i, _vp]),

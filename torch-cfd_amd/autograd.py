@@ -140,6 +140,8 @@ def explicit_terms(op, plan, w_hat: torch.Tensor, forcing_hat) -> torch.Tensor:
     """F(w) = mask * rfft2(-(dx w * u + dy w * v)) + f^  with  psi = -w / lap,  (u, v) = (dy psi, -dx psi).  On the fused
     grids (power-of-two, 3 * 2^k, 5 * 2^k plans) through ``FusedExplicitTerms``; the tensor-op form below serves the composite
     grids and as the cross-check (``TCFD_FUSED_VJP=0``)."""
+    if getattr(op, "_ens_count", 0):   # per-sample forcing rows; the fused VJP is refused on an ensemble plan
+        return _explicit_terms_tensor_ops(op, plan, w_hat, forcing_hat)
     if _fused_vjp_ok(plan):
         if torch.is_grad_enabled() and w_hat.requires_grad:
             return FusedExplicitTerms.apply(w_hat, op, plan)
@@ -165,10 +167,19 @@ def _explicit_terms_tensor_ops(op, plan, w_hat: torch.Tensor, forcing_hat) -> to
     return out
 
 
+def _linear_rows(op, w_hat):
+    """The linear term for the flattened (fields, n, m) state: the (n, m) table, or one (n, m) row per field of an ensemble
+    (member b's row for each of its time slices)."""
+    lin = op.linear_term.to(w_hat.device)
+    if lin.dim() == 3 and lin.shape[0] != w_hat.shape[0]:
+        lin = lin.repeat_interleave(w_hat.shape[0] // lin.shape[0], dim=0)
+    return lin
+
+
 def rk_crank_nicolson_steps(op, plan, w_hat, dt, steps, params, forcing_hat):
     """``steps`` low-storage RK + Crank-Nicolson steps with the coefficient TENSORS of ``params`` (alphas / betas /
     gammas), so that trainable coefficients receive gradients."""
-    lin = op.linear_term.to(w_hat.device)
+    lin = _linear_rows(op, w_hat)
     al, be, ga = (params[k].to(w_hat.device) for k in ("alphas", "betas", "gammas"))
     u = w_hat
     for _ in range(steps):
@@ -359,7 +370,7 @@ class FusedSteps(torch.autograd.Function):
 
 def scheduled_steps(op, plan, w_hat, steps, sched, forcing_hat):
     """The generic stage schedule (``IMEXStepper.stage_schedule``) with detached scalars -- gradients w.r.t. the state."""
-    lin = op.linear_term.to(w_hat.device)
+    lin = _linear_rows(op, w_hat)
     n = len(sched["beta"])
     fa = sched.get("fa") or [1.0] * n
     mu_den = sched.get("mu_den") or sched["mu"]

@@ -153,7 +153,7 @@ static int plan_fill(tcfd_ns2d_plan* p, const double* kx, const double* ky, cons
 extern "C" void tcfd_ns2d_plan_destroy(tcfd_ns2d_plan* p) {
     if (!p) return;
     void* ptrs[] = {p->tw, p->tw2, p->kx, p->ky, p->lin, p->mask, p->forcing, p->mask_r, p->mask_c,
-                    p->lin_r, p->lin_c, p->f_ptr, p->f_row, p->f_val, p->f_col};
+                    p->lin_r, p->lin_c, p->f_ptr, p->f_row, p->f_val, p->f_col, p->ens, p->lap, p->lap_r, p->lap_c};
     for (void* q : ptrs)
         if (q) (void)hipFree(q);
     if (p->prof) {
@@ -277,6 +277,105 @@ extern "C" int tcfd_ns2d_plan_create(tcfd_ns2d_plan** out, int n, int dtype, con
     return 0;
 }
 
+// ------------------------------------------------------------------ per-sample physics
+// One member's linear term nu * lap - drag in the plan's real type, two rounded operations (as the tensor arithmetic that forms a
+// scalar plan's table), and plan_fill's separability test on it: |l[i][j] - (lr[i] + lc[j])| <= 8 eps max|l| with
+// lr[i] = l[i][0] - l[0][0], lc[j] = l[0][j] -- the pair the column kernels form for the member from lap_r / lap_c.
+template <typename T>
+static T member_lin(T nu, T lap, T drag) {
+#pragma clang fp contract(off)
+    const T prod = nu * lap;
+    return prod - drag;
+}
+template <typename T>
+static bool member_separable(const std::vector<T>& lap, int n, int m, T nu, T drag) {
+    T lmax = 0;
+    for (T v : lap) lmax = std::max(lmax, (T)std::fabs(member_lin(nu, v, drag)));
+    const T tol = (T)8 * std::numeric_limits<T>::epsilon() * lmax;
+    const T l00 = member_lin(nu, lap[0], drag);
+    for (int i = 0; i < n; ++i) {
+        const T lr = member_lin(nu, lap[(size_t)i * m], drag) - l00;
+        for (int j = 0; j < m; ++j)
+            if (std::fabs(member_lin(nu, lap[(size_t)i * m + j], drag) - (lr + member_lin(nu, lap[j], drag))) > tol) return false;
+    }
+    return true;
+}
+template <typename T>
+static int ensemble_fill(tcfd_ns2d_plan* p, long count, const double* laplace, const double* nu, const double* drag,
+                         const double* fscale) {
+    const int n = p->n, m = p->m;
+    std::vector<T> lap((size_t)n * m), lr(n), lc(m), tab(4 * (size_t)count);
+    for (size_t e = 0; e < lap.size(); ++e) lap[e] = (T)laplace[e];
+    for (int i = 0; i < n; ++i) lr[i] = lap[(size_t)i * m];
+    for (int j = 0; j < m; ++j) lc[j] = lap[j];
+    bool sep = p->sep != 0;   // the mask is separable and the tables were not forced (plan_fill)
+    for (long b = 0; b < count; ++b) {
+        tab[4 * b] = (T)nu[b];
+        tab[4 * b + 1] = drag ? (T)drag[b] : (T)0;
+        tab[4 * b + 2] = fscale ? (T)fscale[b] : (T)1;
+        // derived, so that a workgroup needs no load of its own for it: the member's l[0][0], subtracted from every lin_r entry
+        tab[4 * b + 3] = member_lin(tab[4 * b], lap[0], tab[4 * b + 1]);
+        if (sep) sep = member_separable(lap, n, m, tab[4 * b], tab[4 * b + 1]);
+    }
+    int rc;
+    if ((rc = upload(&p->ens, tab))) return rc;
+    if ((rc = upload(&p->lap_r, lr))) return rc;
+    if ((rc = upload(&p->lap_c, lc))) return rc;
+    if (!sep && (rc = upload(&p->lap, lap))) return rc;
+    p->ens_sep = sep ? 1 : 0;
+    p->ens_count = count;
+    return 0;
+}
+
+extern "C" int tcfd_ns2d_plan_set_ensemble(tcfd_ns2d_plan* p, long count, const double* laplace, const double* nu,
+                                           const double* drag, const double* forcing_scale) {
+    if (!p) return fail(TCFD_EINVAL, "plan_set_ensemble: null plan");
+    if (count < 0) return fail(TCFD_EINVAL, "plan_set_ensemble: count %ld < 0", count);
+    if (count > 0 && (!laplace || !nu)) return fail(TCFD_EINVAL, "plan_set_ensemble: laplace and nu are required when count > 0");
+    if (count > 0)
+        if (int rc = check_batch(p, count)) return rc;
+    std::lock_guard<std::mutex> lock(p->mu);
+    // a captured step holds pointers into the table: it does not outlive it
+    if (GraphState* g = p->gs) {
+        if (g->exec) { (void)hipGraphExecDestroy(g->exec); g->exec = nullptr; }
+        if (g->graph) { (void)hipGraphDestroy(g->graph); g->graph = nullptr; }
+        if (g->exec_multi) { (void)hipGraphExecDestroy(g->exec_multi); g->exec_multi = nullptr; }
+        if (g->graph_multi) { (void)hipGraphDestroy(g->graph_multi); g->graph_multi = nullptr; }
+        g->ens = nullptr;
+    }
+    // (hipFree waits for the device: no launch of an earlier call still reads the old tables)
+    void** tabs[] = {&p->ens, &p->lap, &p->lap_r, &p->lap_c};
+    for (void** q : tabs)
+        if (*q) { (void)hipFree(*q); *q = nullptr; }
+    p->ens_count = 0;
+    p->ens_sep = 0;
+    if (count == 0) return 0;   // a scalar plan again: the tables of plan_create
+    int rc = p->dtype == TCFD_C128 ? ensemble_fill<double>(p, count, laplace, nu, drag, forcing_scale)
+                                   : ensemble_fill<float>(p, count, laplace, nu, drag, forcing_scale);
+    if (rc) {   // never half an ensemble
+        for (void** q : tabs)
+            if (*q) { (void)hipFree(*q); *q = nullptr; }
+        p->ens_count = 0;
+        p->ens_sep = 0;
+    }
+    return rc;
+}
+
+// an ensemble plan steps exactly its own members, one field each
+static int check_ensemble_batch(const tcfd_ns2d_plan* p, long batch, const char* what) {
+    if (p->ens_count > 0 && batch != p->ens_count)
+        return fail(TCFD_EINVAL, "%s: batch %ld on a plan with per-sample parameters for %ld fields (tcfd_ns2d_plan_set_ensemble)",
+                    what, batch, p->ens_count);
+    return 0;
+}
+// the tangent-linear, adjoint and refiner kernels read ONE linear-term table
+static int refuse_ensemble(const tcfd_ns2d_plan* p, const char* what) {
+    if (p->ens_count > 0)
+        return fail(TCFD_EINVAL, "%s: not implemented for a plan with per-sample parameters (tcfd_ns2d_plan_set_ensemble, %ld "
+                    "fields): the tangent-linear, adjoint and refiner kernels read one linear-term table", what, p->ens_count);
+    return 0;
+}
+
 extern "C" int tcfd_ns2d_plan_info(const tcfd_ns2d_plan* p, int* separable, int* sparse_forcing, int* keep_cols) {
     if (!p) return fail(TCFD_EINVAL, "plan_info: null plan");
     if (separable) *separable = p->sep;
@@ -339,6 +438,7 @@ extern "C" int tcfd_ns2d_step_imex(const tcfd_ns2d_plan* p, const void* w_in, vo
     if (!p || !w_in || !w_out || !beta || !gdt || !mu_num) return fail(TCFD_EINVAL, "step: null argument");
     if (batch <= 0 || steps <= 0 || nstages <= 0) return fail(TCFD_EINVAL, "step: batch/steps/nstages must be > 0");
     if (dwdt && w_in == w_out) return fail(TCFD_EINVAL, "step: w_out may alias w_in only when dwdt is NULL");
+    if (int rce = check_ensemble_batch(p, batch, "step")) return rce;
     int rc = check_ws(p, batch, ws, ws_bytes, tcfd_ns2d_workspace_bytes(p, batch));
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -354,13 +454,13 @@ extern "C" int tcfd_ns2d_step_imex(const tcfd_ns2d_plan* p, const void* w_in, vo
             const unsigned char* in = (const unsigned char*)w_in + b0 * esz;
             unsigned char* out = (unsigned char*)w_out + b0 * esz;
             unsigned char* dw = dwdt ? (unsigned char*)dwdt + b0 * esz : nullptr;
-            rc = NS2D_SIZED(p, step, p, in, out, dw, nb, nstages, beta, gdt, mu_num, fa, mu_den, base0, steps, inv_total_dt, ws, st);
+            rc = NS2D_SIZED(p, step, p, in, out, dw, nb, nstages, beta, gdt, mu_num, fa, mu_den, base0, steps, inv_total_dt, ws, st, b0);
             if (rc) return rc;
         }
         return 0;
     }
     return NS2D_SIZED(p, step, p, w_in, w_out, dwdt, batch, nstages, beta, gdt, mu_num, fa, mu_den, base0, steps, inv_total_dt, ws,
-                      st);
+                      st, 0L);
 }
 
 extern "C" int tcfd_ns2d_step(const tcfd_ns2d_plan* p, const void* w_in, void* w_out, void* dwdt, long batch,
@@ -374,14 +474,14 @@ extern "C" int tcfd_ns2d_step(const tcfd_ns2d_plan* p, const void* w_in, void* w
 int ns2d::explicit_chunked(const tcfd_ns2d_plan* p, const void* w, void* out, const void* wt, void* psi, bool residual,
                            long batch, void* ws, hipStream_t st) {
     const long chunk = chunk_fields(p, batch);
-    if (chunk >= batch) return NS2D_SIZED(p, explicit_terms, p, w, out, wt, psi, residual, batch, ws, st);
+    if (chunk >= batch) return NS2D_SIZED(p, explicit_terms, p, w, out, wt, psi, residual, batch, ws, st, 0L);
     const size_t esz = (p->dtype == TCFD_C128 ? 16 : 8) * (size_t)p->n * p->m;
     auto at = [&](const void* base, long b0) -> unsigned char* {
         return base ? (unsigned char*)base + (size_t)b0 * esz : nullptr;
     };
     for (long b0 = 0; b0 < batch; b0 += chunk) {
         const long nb = std::min(chunk, batch - b0);
-        int rc = NS2D_SIZED(p, explicit_terms, p, at(w, b0), at(out, b0), at(wt, b0), at(psi, b0), residual, nb, ws, st);
+        int rc = NS2D_SIZED(p, explicit_terms, p, at(w, b0), at(out, b0), at(wt, b0), at(psi, b0), residual, nb, ws, st, b0);
         if (rc) return rc;
     }
     return 0;
@@ -390,6 +490,7 @@ int ns2d::explicit_chunked(const tcfd_ns2d_plan* p, const void* w, void* out, co
 extern "C" int tcfd_ns2d_explicit_terms(const tcfd_ns2d_plan* p, const void* w, void* out, long batch, void* ws,
                                         size_t ws_bytes, void* stream) {
     if (!p || !w || !out || batch <= 0) return fail(TCFD_EINVAL, "explicit_terms: bad argument");
+    if (int rce = check_ensemble_batch(p, batch, "explicit_terms")) return rce;
     int rc = check_ws(p, batch, ws, ws_bytes, tcfd_ns2d_workspace_bytes(p, batch));
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -399,6 +500,7 @@ extern "C" int tcfd_ns2d_explicit_terms(const tcfd_ns2d_plan* p, const void* w, 
 extern "C" int tcfd_ns2d_explicit_terms_vjp(const tcfd_ns2d_plan* p, const void* w, const void* gm, void* xout, long batch,
                                             void* ws, size_t ws_bytes, void* stream) {
     if (!p || !w || !gm || !xout || batch <= 0) return fail(TCFD_EINVAL, "explicit_terms_vjp: bad argument");
+    if (int rce = refuse_ensemble(p, "explicit_terms_vjp")) return rce;
     int rc = check_ws(p, batch, ws, ws_bytes, tcfd_ns2d_workspace_bytes(p, batch));
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -432,6 +534,7 @@ extern "C" size_t tcfd_ns2d_jvp_workspace_bytes(const tcfd_ns2d_plan* p, long ba
 extern "C" int tcfd_ns2d_explicit_terms_jvp(const tcfd_ns2d_plan* p, const void* w, const void* dw, void* out_f, void* out_df,
                                             long batch, void* ws, size_t ws_bytes, void* stream) {
     if (!p || !w || !dw || !out_df || batch <= 0) return fail(TCFD_EINVAL, "explicit_terms_jvp: bad argument");
+    if (int rce = refuse_ensemble(p, "explicit_terms_jvp")) return rce;
     int rc = check_ws(p, batch, ws, ws_bytes, tcfd_ns2d_jvp_workspace_bytes(p, batch));
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -453,6 +556,7 @@ extern "C" int tcfd_ns2d_step_jvp(const tcfd_ns2d_plan* p, const void* w_in, con
                                   size_t ws_bytes, void* stream) {
     if (!p || !w_in || !dw_in || !w_out || !dw_out || !beta || !gdt || !mu_num) return fail(TCFD_EINVAL, "step_jvp: null argument");
     if (batch <= 0 || steps <= 0 || nstages <= 0) return fail(TCFD_EINVAL, "step_jvp: batch/steps/nstages must be > 0");
+    if (int rce = refuse_ensemble(p, "step_jvp")) return rce;
     if (w_out == dw_out || w_out == dw_in || dw_out == w_in)
         return fail(TCFD_EINVAL, "step_jvp: the state and the tangent arrays must not overlap");
     int rc = check_ws(p, batch, ws, ws_bytes, tcfd_ns2d_jvp_workspace_bytes(p, batch));
@@ -485,6 +589,7 @@ extern "C" int tcfd_ns2d_step_vjp(const tcfd_ns2d_plan* p, const void* saved, co
     if (!p || !saved || !g_out || !pre || !post || !g_in || !beta || !gdt || !mu_num)
         return fail(TCFD_EINVAL, "step_vjp: null argument");
     if (batch <= 0) return fail(TCFD_EINVAL, "step_vjp: batch must be > 0");
+    if (int rce = refuse_ensemble(p, "step_vjp")) return rce;
     if (steps <= 0) return fail(TCFD_EINVAL, "step_vjp: steps must be > 0 (got %d)", steps);
     if (nstages <= 0 || nstages > VJP_MAX_STAGES)
         return fail(TCFD_EINVAL, "step_vjp: nstages %d out of range [1, %d]", nstages, VJP_MAX_STAGES);
@@ -517,6 +622,7 @@ extern "C" int tcfd_ns2d_step_vjp(const tcfd_ns2d_plan* p, const void* saved, co
 extern "C" int tcfd_ns2d_stream_residual(const tcfd_ns2d_plan* p, const void* w, const void* wt, void* psi,
                                          void* residual, long batch, void* ws, size_t ws_bytes, void* stream) {
     if (!p || !w || batch <= 0 || (residual && !wt)) return fail(TCFD_EINVAL, "stream_residual: bad argument");
+    if (int rce = check_ensemble_batch(p, batch, "stream_residual")) return rce;
     int rc = check_ws(p, batch, ws, ws_bytes, tcfd_ns2d_workspace_bytes(p, batch));
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;

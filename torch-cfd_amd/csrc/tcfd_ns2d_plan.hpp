@@ -49,6 +49,7 @@ struct GraphState {
     int nstages = 0;
     void* ws = nullptr;
     std::vector<double> coef;
+    const void* ens = nullptr;   // the chunk's slice of the plan's ensemble table (null on a scalar plan)
 };
 
 // Tuning switches (environment, read ONCE at plan creation and frozen in the plan: two plans of one process may
@@ -104,6 +105,12 @@ struct tcfd_ns2d_plan {
     int nyq_a, nyq_ca;   // ... in the opening pass / in the fused passes of a step (set with nyq at plan creation)
     int nyq;        // packed Nyquist column in the step kernels (emit_planes): the plan is pruned (F = h = 0 in column
                     // m - 1), n >= 64 (every column tile width divides n / 2) and the row kernels are v5 / v7
+    // per-sample physics (tcfd_ns2d_plan_set_ensemble; all null / 0 on a scalar plan, whose kernels then run as before)
+    void* ens;      // T[4 * ens_count]: {nu, drag, forcing_scale, l00 = nu * lap[0][0] - drag} per field of a call
+    long ens_count; // > 0: the plan steps ensembles of exactly this many fields
+    void* lap;      // T[n*m] laplacian (uploaded only when the separable form is not used)
+    void* lap_r; void* lap_c;   // T[n] its column 0, T[m] its row 0
+    int ens_sep;    // every member's nu * lap - drag passes plan_fill's separability test (and the mask is separable)
     int keep_cols;  // > 0: F (hence the RK accumulator h) is identically zero for columns >= keep_cols and for
                     // rows with mask_r == 0 (2/3-rule mask, forcing inside the mask): those entries of the
                     // advection / h arrays are neither written nor read.  0: no pruning.
@@ -272,10 +279,11 @@ template <typename T> int fill_round_fields(tcfd_ns2d_plan* p);
 template <typename T>
 int step(const tcfd_ns2d_plan* p, const void* w_in, void* w_out, void* dwdt, long batch, int nstages, const double* beta,
          const double* gdt, const double* mu_num, const double* fa, const double* mu_den, const int* base0, int steps,
-         double inv_total_dt, void* ws, hipStream_t st);
+         double inv_total_dt, void* ws, hipStream_t st, long ens_b0);
+// ens_b0: position of the chunk's first field in the caller's batch (the row of an ensemble plan's table it steps with)
 template <typename T>
 int explicit_terms(const tcfd_ns2d_plan* p, const void* w, void* out, const void* wt, void* psi, bool residual, long batch,
-                   void* ws, hipStream_t st);
+                   void* ws, hipStream_t st, long ens_b0);
 template <typename T>
 int explicit_vjp(const tcfd_ns2d_plan* p, const void* w, const void* gm, void* xout, size_t x_field_stride, long batch, void* ws,
                  hipStream_t st);

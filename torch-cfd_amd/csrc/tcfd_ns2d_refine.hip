@@ -301,6 +301,9 @@ extern "C" int tcfd_ns2d_refine(const tcfd_ns2d_plan* p, const void* w, const vo
                               void* res_out, long batch, int nt, double dt, double visc, double bdf0, double bdf1, void* ws,
                               size_t ws_bytes, void* stream) {
     if (!p || !w || batch <= 0 || nt <= 0 || dt == 0.0) return fail(TCFD_EINVAL, "refine: bad argument");
+    if (p->ens_count > 0)
+        return fail(TCFD_EINVAL, "refine: not implemented for a plan with per-sample parameters (tcfd_ns2d_plan_set_ensemble): the "
+                    "refiner reads one linear-term table");
     if (int rc_ = check_batch(p, batch * nt)) return rc_;   // every (sample, step) slice is one field of the sweeps
     int rc = check_ws(p, batch, ws, ws_bytes, tcfd_ns2d_refine_workspace_bytes(p, batch, nt));
     if (rc) return rc;
@@ -314,6 +317,9 @@ extern "C" int tcfd_ns2d_refine_vjp(const tcfd_ns2d_plan* p, const void* w, cons
                                   const void* g_res, void* grad_w, void* grad_f_hat, long batch, int nt, double dt, double visc,
                                   double bdf0, double bdf1, void* ws, size_t ws_bytes, void* stream) {
     if (!p || !w || batch <= 0 || nt <= 0 || dt == 0.0) return fail(TCFD_EINVAL, "refine_vjp: bad argument");
+    if (p->ens_count > 0)
+        return fail(TCFD_EINVAL, "refine_vjp: not implemented for a plan with per-sample parameters (tcfd_ns2d_plan_set_ensemble): the "
+                    "refiner reads one linear-term table");
     if (grad_f_hat && !f_hat) return fail(TCFD_EINVAL, "refine_vjp: grad_f_hat needs f_hat");
     if (int rc_ = check_batch(p, batch * nt)) return rc_;
     int rc = check_ws(p, batch, ws, ws_bytes, tcfd_ns2d_refine_workspace_bytes(p, batch, nt));

@@ -155,7 +155,27 @@ struct ColArgs {
                    // the non-temporal hint they do not push the next chunk's working set out of the Infinity Cache
     int pair_xcd;  // block->tile map: 0 = batch fastest; LG = 2 / 4 / 8: the LG tiles that share a 128-byte line on one XCD
     cx<T>* h_out;  // RK accumulator write (NULL: == h)
+    // per-sample physics (tcfd_ns2d_plan_set_ensemble): {nu, drag, forcing_scale, l00} of the launch's field 0 onwards, or null.  When
+    // set, lin / lin_r / lin_c hold the LAPLACIAN (dense, its column 0 and its row 0) and field b steps with
+    // L = nu_b * LAP - drag_b (two rounded operations) and forcing_scale_b * forcing; the drivers point it at the chunk's first field
+    const T* ens;
+    int lsep;      // 1: the linear term in its separable form (== sep on a scalar plan; an ensemble plan tests every member)
 };
+
+// fl(fl(nu * lap) - drag): the linear term of one ensemble member, rounded as the element-wise tensor arithmetic that forms
+// the (n, m) table of a scalar plan rounds it (no contraction into a fused multiply-add)
+template <typename T>
+__device__ __forceinline__ T ens_lin(T nu, T lap, T drag) {
+#pragma clang fp contract(off)
+    const T prod = nu * lap;
+    return prod - drag;
+}
+// forcing_scale * f, rounded once before the sum that takes it
+template <typename T>
+__device__ __forceinline__ cx<T> ens_force(const cx<T> f, T s) {
+#pragma clang fp contract(off)
+    return tcfd::mk<T>(f.x * s, f.y * s);
+}
 
 // SP = 1 ("split"): the workgroup owns the rows of ONE parity q of the column (i = 2 s + q) and runs N/2-point
 // transforms on them; the radix-2 butterfly that joins the two parities rides in the row kernel, which works
@@ -314,10 +334,11 @@ __device__ __forceinline__ void emit_planes(const ColArgs<T>& a, const cx<T> (&u
 }
 
 // x[t] (column FFT of the advection) -> F = mask * x + forcing, in place (equations.py:424-437)
-template <typename T, int N, int EPT, int SP>
+template <typename T, int N, int EPT, int SP, int ENS>
 __device__ __forceinline__ void apply_mask_forcing(const ColArgs<T>& a, cx<T> (&x)[EPT], int j, int jc,
-                                                   const T* rt_mask, T cm, int f_lo, int f_hi, int q) {
+                                                   const T* rt_mask, T cm, int f_lo, int f_hi, int q, T fs) {
     constexpr int G = (N >> SP) / EPT;
+    // ENS: the member's forcing is fs * forcing (fs is workgroup-uniform)
 #define TCFD_IROW(t_) (SP ? 2 * (j + (t_) * G) + q : j + (t_) * G)
     if (a.ablate & 4) return;
     if (a.sep) {
@@ -331,7 +352,8 @@ __device__ __forceinline__ void apply_mask_forcing(const ColArgs<T>& a, cx<T> (&
         for (int e = 0; e < a.f_nnz; ++e) {
             const int r = a.f_row[e];
             const int fc = a.f_col[e];      // all three reads of an entry before the branch: one round trip, not two
-            const cx<T> v = a.f_val[e];
+            cx<T> v = a.f_val[e];
+            if constexpr (ENS) v = ens_force(v, fs);
             if (fc == jc) {
 #pragma unroll
                 for (int t = 0; t < EPT; ++t)
@@ -341,21 +363,29 @@ __device__ __forceinline__ void apply_mask_forcing(const ColArgs<T>& a, cx<T> (&
     } else if (a.f_ptr) {  // sparse, many entries: this column's slice of the CSC list
         for (int e = f_lo; e < f_hi; ++e) {
             const int r = a.f_row[e];
-            const cx<T> v = a.f_val[e];
+            cx<T> v = a.f_val[e];
+            if constexpr (ENS) v = ens_force(v, fs);
 #pragma unroll
             for (int t = 0; t < EPT; ++t)
                 if (r == TCFD_IROW(t)) x[t] = x[t] + v;
         }
     } else if (a.forcing) {
 #pragma unroll
-        for (int t = 0; t < EPT; ++t) x[t] = x[t] + a.forcing[(size_t)TCFD_IROW(t) * a.m + jc];
+        for (int t = 0; t < EPT; ++t) {
+            cx<T> v = a.forcing[(size_t)TCFD_IROW(t) * a.m + jc];
+            if constexpr (ENS) v = ens_force(v, fs);
+            x[t] = x[t] + v;
+        }
     }
 #undef TCFD_IROW
 }
 
 // NYQ = 1: the variant that can run with a.nyq (packed Nyquist column); kept apart because the extra code costs the
 // register-capped fp64 kernels a few spilled registers in EVERY workgroup, packed or not
-template <typename T, int N, int EPT, int C, int MODE, int MINW, int SP = 0, int XL = 0, int NYQ = 0>
+// ENS = 1: per-sample physics (a.ens is set; MODE_CA / C / F / RES).  Its own instantiations for the same reason: as a
+// workgroup-uniform branch the member arithmetic moved the register count of most scalar kernels and cost several of them a wave
+// of occupancy (profiles/ns2d_ensemble_kernel_resource_usage.txt); with ENS = 0 the kernel is the one it was
+template <typename T, int N, int EPT, int C, int MODE, int MINW, int SP = 0, int XL = 0, int NYQ = 0, int ENS = 0>
 __global__ __launch_bounds__(C*((N >> SP) / EPT), MINW) void k_cols(ColArgs<T> a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     cx<T>* lds = reinterpret_cast<cx<T>*>(smem_raw);
@@ -392,6 +422,19 @@ __global__ __launch_bounds__(C*((N >> SP) / EPT), MINW) void k_cols(ColArgs<T> a
     }
     const int jc = tile * C + c;
     const bool valid = jc < a.m;
+    // the member's {nu, drag, forcing scale}: b is workgroup-uniform, so these are three uniform loads into scalar registers
+    // (and l00 = nu * LAP[0][0] - drag, which the host formed with the same two roundings: no dependent load for it here)
+    [[maybe_unused]] T e_nu = 1, e_drag = 0, e_fs = 1, e_l00 = 0;
+    if constexpr (ENS) {
+        const T* e = a.ens + 4 * (size_t)b;
+        e_nu = e[0]; e_drag = e[1]; e_fs = e[2]; e_l00 = e[3];
+    }
+    // the linear term from a table entry: the entry itself, or (ensemble) the member's nu * laplacian - drag
+    [[maybe_unused]] auto lin_of = [&](T raw) -> T {
+        if constexpr (ENS) return ens_lin(e_nu, raw, e_drag);
+        else return raw;
+    };
+    const int lsep = ENS ? a.lsep : a.sep;   // (a scalar plan: one flag for the mask and the linear term)
     const bool nyq_tile = NYQ && a.nyq && tile == 0;   // block-uniform: the lanes c == 0 of this workgroup also own column m - 1
     const bool nyq_lane = nyq_tile && c == 0;
     const size_t colbase = (size_t)b * N * a.m + jc;   // element (b, 0, jc) of a caller-layout array
@@ -415,18 +458,28 @@ __global__ __launch_bounds__(C*((N >> SP) / EPT), MINW) void k_cols(ColArgs<T> a
     // the tile's loads instead of behind the transform.)
     auto stage_tables = [&]() {
         if constexpr (NEEDS_TABLES) {
-            const T* lin_r = a.sep ? a.lin_r : a.kx;
+            const T* lin_r = lsep ? a.lin_r : a.kx;
             const T* mask_r = a.sep ? a.mask_r : a.kx;
+            // ensemble: lin_r[i] + lin_c[j] of the member, formed from the laplacian's column 0 and row 0 as plan_fill forms a
+            // scalar plan's pair from its table (lin_r[i] = l[i][0] - l[0][0], lin_c[j] = l[0][j]): the same bits
             for (int sl = threadIdx.x; sl < NT; sl += C * G) {  // indexed by the LOCAL row sl, spectral row IROW(sl)
                 const int i = TCFD_IROW(sl);
                 const T vk = a.kx[i], vl = lin_r[i], vm = mask_r[i];
                 rt_kx[sl] = vk;
-                rt_lin[sl] = a.sep ? vl : (T)0;
+                if constexpr (ENS) rt_lin[sl] = lsep ? ens_lin(e_nu, vl, e_drag) - e_l00 : (T)0;
+                else rt_lin[sl] = a.sep ? vl : (T)0;
                 rt_mask[sl] = a.sep ? vm : (T)1;
             }
             if (valid) {
                 col_ky = a.ky[jc];
-                if (a.sep) { col_lin = a.lin_c[jc]; col_mask = a.mask_c[jc]; }
+                if constexpr (ENS) {
+                    // the laplacian's entry as loaded; lin_of is applied where L is formed: arithmetic on the value HERE makes
+                    // the wave wait for this load -- and for the tile's loads issued before it -- ahead of the loads that follow
+                    if (lsep) col_lin = a.lin_c[jc];
+                    if (a.sep) col_mask = a.mask_c[jc];
+                } else {
+                    if (a.sep) { col_lin = a.lin_c[jc]; col_mask = a.mask_c[jc]; }
+                }
                 if (a.f_ptr && a.f_nnz == 0) { f_lo = a.f_ptr[jc]; f_hi = a.f_ptr[jc + 1]; }
             }
         }
@@ -481,7 +534,7 @@ __global__ __launch_bounds__(C*((N >> SP) / EPT), MINW) void k_cols(ColArgs<T> a
             return;
         } else if constexpr (MODE == MODE_F) {
             if (valid) {
-                apply_mask_forcing<T, N, EPT, SP>(a, x, j, jc, rt_mask, col_mask, f_lo, f_hi, q);
+                apply_mask_forcing<T, N, EPT, SP, ENS>(a, x, j, jc, rt_mask, col_mask, f_lo, f_hi, q, e_fs);
 #pragma unroll
                 for (int t = 0; t < EPT; ++t) a.out[colbase + (size_t)TCFD_IROW(j + t * G) * a.m] = x[t];
             }
@@ -490,8 +543,8 @@ __global__ __launch_bounds__(C*((N >> SP) / EPT), MINW) void k_cols(ColArgs<T> a
             if (valid) {
                 constexpr T M4PI2 = (T)(-39.478417604357434475337963999505);
                 const T ky = col_ky;
-                apply_mask_forcing<T, N, EPT, SP>(a, x, j, jc, rt_mask, col_mask, f_lo, f_hi, q);
-                const T lc = col_lin;
+                apply_mask_forcing<T, N, EPT, SP, ENS>(a, x, j, jc, rt_mask, col_mask, f_lo, f_hi, q, e_fs);
+                const T lc = lin_of(col_lin);
 #pragma unroll
                 for (int t = 0; t < EPT; ++t) {
                     const int sl = j + t * G;
@@ -501,7 +554,7 @@ __global__ __launch_bounds__(C*((N >> SP) / EPT), MINW) void k_cols(ColArgs<T> a
                     const cx<T> w = a.u_in[g];
                     if (a.out) {
                         const cx<T> wt = a.wt[g];
-                        const T L = a.sep ? rt_lin[sl] + lc : a.lin[(size_t)i * a.m + jc];
+                        const T L = lsep ? rt_lin[sl] + lc : lin_of(a.lin[(size_t)i * a.m + jc]);
                         a.out[g] = wt - F - cscale(w, L);
                     }
                     if (a.psi) {
@@ -537,9 +590,9 @@ __global__ __launch_bounds__(C*((N >> SP) / EPT), MINW) void k_cols(ColArgs<T> a
                 // a load written after an earlier element's store is not moved above it -- 2 EPT memory round trips
                 // one after the other.  In the cache-resident regimes (chunked 1024^2, small grids) a workgroup's
                 // dependency chain IS the kernel time.
-                const T lc = col_lin;
+                const T lc = lin_of(col_lin);
                 const size_t ub = (size_t)b * N * a.u_in_ld + jc;
-                apply_mask_forcing<T, N, EPT, SP>(a, x, j, jc, rt_mask, col_mask, f_lo, f_hi, q);
+                apply_mask_forcing<T, N, EPT, SP, ENS>(a, x, j, jc, rt_mask, col_mask, f_lo, f_hi, q, e_fs);
                 // UB elements per batch of reads: everything at once where the registers are there (fp32, short
                 // columns), 64 bytes' worth per array otherwise (the long-column kernels sit at the 128-register cap)
                 constexpr int UB = EPT * (int)sizeof(cx<T>) <= 64 ? EPT : 64 / (int)sizeof(cx<T>);   // 8 fp32 / 4 fp64
@@ -557,7 +610,7 @@ __global__ __launch_bounds__(C*((N >> SP) / EPT), MINW) void k_cols(ColArgs<T> a
                         h_live[tt] = !(a.ablate & 8) && (a.keep_cols == 0 || (col_live && rt_mask[sl] != (T)0));
                         hv[tt] = (h_live[tt] && a.load_h) ? a.h[wbase + (wq + (size_t)sl) * a.ldw] : mk<T>((T)0, (T)0);
                         uv[tt] = a.u_in[ub + (size_t)i * a.u_in_ld];
-                        Lv[tt] = (a.ablate & 4) ? (T)-0.5 : (a.sep ? rt_lin[sl] + lc : a.lin[(size_t)i * a.m + jc]);
+                        Lv[tt] = (a.ablate & 4) ? (T)-0.5 : (lsep ? rt_lin[sl] + lc : lin_of(a.lin[(size_t)i * a.m + jc]));
                         if constexpr (MODE == MODE_C) {
                             if (a.dwdt) w0v[tt] = a.w0[(size_t)b * N * a.m + jc + (size_t)i * a.m];
                         }
@@ -598,7 +651,7 @@ __global__ __launch_bounds__(C*((N >> SP) / EPT), MINW) void k_cols(ColArgs<T> a
                 // column m - 1, a row per thread: F = 0 there (the plan is pruned: keep_cols <= m - 1), so h stays 0 and
                 // the stage is  u <- (u + mu L u) / (1 - mud L)
                 const int jn = a.m - 1;
-                const T lcn = a.sep ? a.lin_c[jn] : (T)0;
+                const T lcn = lsep ? lin_of(a.lin_c[jn]) : (T)0;
                 constexpr int PER = NYQ_PER;
                 cx<T> unew[PER];
 #pragma unroll
@@ -607,7 +660,7 @@ __global__ __launch_bounds__(C*((N >> SP) / EPT), MINW) void k_cols(ColArgs<T> a
                     if (sl < NT) {
                         const int i = TCFD_IROW(sl);
                         const cx<T> uo = nyq_u[r];
-                        const T L = (a.ablate & 4) ? (T)-0.5 : (a.sep ? rt_lin[sl] + lcn : a.lin[(size_t)i * a.m + jn]);
+                        const T L = (a.ablate & 4) ? (T)-0.5 : (lsep ? rt_lin[sl] + lcn : lin_of(a.lin[(size_t)i * a.m + jn]));
                         const cx<T> rhs = uo + cscale(cscale(uo, L), a.mu);
                         unew[r] = cscale(rhs, fast_rcp((T)1 - a.mud * L));
                         if (writer) a.u_out[(size_t)b * N * a.u_out_ld + jn + (size_t)i * a.u_out_ld] = unew[r];
@@ -1292,6 +1345,12 @@ static int line_group(const tcfd_ns2d_plan* p) {
     return p->tune.pair_xcd == 2 ? 2 : lg;
 }
 
+// {nu, drag, forcing_scale, l00} of field `b0` of the caller's batch on an ensemble plan (a chunk or a half batch starts there), else null
+template <typename T>
+static const T* ens_at(const tcfd_ns2d_plan* p, long b0) {
+    return p->ens ? (const T*)p->ens + 4 * (size_t)b0 : nullptr;
+}
+
 template <typename T, int N, int MODE, int EPT, int C, int MINW = 1, int SP = 0>
 static int launch_cols_v(const tcfd_ns2d_plan* p, ColArgs<T> a, long batch, hipStream_t st, bool no_forcing = false) {
     constexpr int NT = N >> SP;
@@ -1323,6 +1382,15 @@ static int launch_cols_v(const tcfd_ns2d_plan* p, ColArgs<T> a, long batch, hipS
         a.f_nnz = 0;
     }
     a.sep = p->sep;
+    a.lsep = p->sep;
+    constexpr bool ENS_MODE = (MODE == MODE_CA || MODE == MODE_C || MODE == MODE_F || MODE == MODE_RES);
+    if (!ENS_MODE) a.ens = nullptr;   // the other passes read neither L nor the forcing
+    if (a.ens) {   // per-sample physics: the kernels form L from the laplacian's tables (tcfd_ns2d_plan_set_ensemble)
+        a.lin = (const T*)p->lap;
+        a.lin_r = (const T*)p->lap_r;
+        a.lin_c = (const T*)p->lap_c;
+        a.lsep = p->ens_sep;
+    }
     a.keep_cols = p->keep_cols;
     a.tw = (const cx<T>*)(SP ? p->tw2 : p->tw);
     a.pair_xcd = line_group<T, C>(p);
@@ -1350,6 +1418,13 @@ static int launch_cols_v(const tcfd_ns2d_plan* p, ColArgs<T> a, long batch, hipS
             lds = col_lds_bytes<T, NT, EPT, C>(xl_col_direct<T>()) + (size_t)p->tune.cols_lds_pad;   // + the stage-two roots
             a.nt_planes = p->tune.nt_planes > 0;
             static DevOnce once_x, once_xn;
+            if constexpr (ENS_MODE) {   // per-sample physics: the ENS instantiations
+                static DevOnce once_xe, once_xne;
+                if constexpr (NYQ_MODE) {
+                    if (a.ens && a.nyq) return launch(k_cols<T, N, EPT, C, MODE, MINW, SP, 1, 1, 1>, once_xne);
+                }
+                if (a.ens) return launch(k_cols<T, N, EPT, C, MODE, MINW, SP, 1, 0, 1>, once_xe);
+            }
             if constexpr (NYQ_MODE) {
                 if (a.nyq) return launch(k_cols<T, N, EPT, C, MODE, MINW, SP, 1, 1>, once_xn);
             }
@@ -1361,6 +1436,13 @@ static int launch_cols_v(const tcfd_ns2d_plan* p, ColArgs<T> a, long batch, hipS
     // (at 1024^2 the same hint costs 1-3 %)
     a.nt_planes = p->tune.nt_planes >= 0 ? p->tune.nt_planes : (C == 4 && EPT == 4);
     static DevOnce once, once_n;
+    if constexpr (ENS_MODE) {
+        static DevOnce once_e, once_ne;
+        if constexpr (NYQ_MODE) {
+            if (a.ens && a.nyq) return launch(k_cols<T, N, EPT, C, MODE, MINW, SP, 0, 1, 1>, once_ne);
+        }
+        if (a.ens) return launch(k_cols<T, N, EPT, C, MODE, MINW, SP, 0, 0, 1>, once_e);
+    }
     if constexpr (NYQ_MODE) {
         if (a.nyq) return launch(k_cols<T, N, EPT, C, MODE, MINW, SP, 0, 1>, once_n);
     }
@@ -1541,7 +1623,7 @@ template <typename T, int N>
 static int step_overlap_impl(const tcfd_ns2d_plan* p, const void* w_in, void* w_out, void* dwdt, long batch, int nstages,
                              const double* beta, const double* gdt, const double* mu, const double* fa,
                              const double* mud, const int* base0, int steps, double inv_total_dt, void* ws,
-                             hipStream_t st) {
+                             hipStream_t st, long ens_b0) {
     tcfd_ns2d_plan* mp = const_cast<tcfd_ns2d_plan*>(p);
     std::lock_guard<std::mutex> lock(mp->mu);   // the plan-owned streams / events serve one call at a time
     if (!mp->gs) mp->gs = new GraphState();
@@ -1576,6 +1658,7 @@ static int step_overlap_impl(const tcfd_ns2d_plan* p, const void* w_in, void* w_
         h.dwdt = dwdt ? (cx<T>*)dwdt + oc : nullptr;
         h.planes = W.planes + ow; h.adv = W.adv + ow; h.upad = W.upad + ow; h.upad2 = W.upad2 + ow;
         h.a = ColArgs<T>{};
+        h.a.ens = ens_at<T>(p, ens_b0 + b0);
         h.a.nyq = p->nyq_a;
         h.a.planes = h.planes; h.a.plane_stride = W.plane_stride; h.a.h = W.h + ow; h.a.in = h.adv;
         h.a.u_in = h.w_in; h.a.u_in_ld = p->m;
@@ -1637,17 +1720,18 @@ static int step_overlap_impl(const tcfd_ns2d_plan* p, const void* w_in, void* w_
 template <typename T, int N>
 static int step_impl(const tcfd_ns2d_plan* p, const void* w_in, void* w_out, void* dwdt, long batch, int nstages,
                      const double* beta, const double* gdt, const double* mu, const double* fa, const double* mud,
-                     const int* base0, int steps, double inv_total_dt, void* ws, hipStream_t st) {
+                     const int* base0, int steps, double inv_total_dt, void* ws, hipStream_t st, long ens_b0) {
     {
         // opt-in (TCFD_OVERLAP=1): measured +2.6 % at 1024^2 x 64 fp64 -- both kernels fill the VGPR file, so the CUs
         // time-slice the two halves instead of co-running them; not worth two streams by default
         if (batch >= 2 && p->tune.overlap == 1)
             return step_overlap_impl<T, N>(p, w_in, w_out, dwdt, batch, nstages, beta, gdt, mu, fa, mud, base0, steps,
-                                           inv_total_dt, ws, st);
+                                           inv_total_dt, ws, st, ens_b0);
     }
     Ws<T> W = carve<T>(p, ws, batch);
     int rc;
     ColArgs<T> a{};
+    a.ens = ens_at<T>(p, ens_b0);
     a.planes = W.planes;
     a.plane_stride = W.plane_stride;
     a.h = W.h;
@@ -1739,13 +1823,14 @@ static int step_impl(const tcfd_ns2d_plan* p, const void* w_in, void* w_out, voi
             HIP_TRY(hipGraphInstantiate(exec, *graph, nullptr, nullptr, 0));
             return 0;
         };
-        if (!g->exec || g->batch != batch || g->nstages != nstages || g->ws != ws || g->coef != coef) {
+        // (the captured launches hold the chunk's slice of the ensemble table: another chunk, or a table set anew, is another graph)
+        if (!g->exec || g->batch != batch || g->nstages != nstages || g->ws != ws || g->coef != coef || g->ens != (const void*)a.ens) {
             if (g->exec) { (void)hipGraphExecDestroy(g->exec); g->exec = nullptr; }
             if (g->graph) { (void)hipGraphDestroy(g->graph); g->graph = nullptr; }
             if (g->exec_multi) { (void)hipGraphExecDestroy(g->exec_multi); g->exec_multi = nullptr; }
             if (g->graph_multi) { (void)hipGraphDestroy(g->graph_multi); g->graph_multi = nullptr; }
             if ((rc = capture(1, &g->graph, &g->exec))) return rc;
-            g->batch = batch; g->nstages = nstages; g->ws = ws; g->coef = coef;
+            g->batch = batch; g->nstages = nstages; g->ws = ws; g->coef = coef; g->ens = a.ens;
         }
         int interior = steps - 2;
         if (interior >= 2 * GraphState::MULTI && !g->exec_multi &&
@@ -1768,10 +1853,11 @@ static int step_impl(const tcfd_ns2d_plan* p, const void* w_in, void* w_out, voi
 
 template <typename T, int N>
 static int explicit_impl(const tcfd_ns2d_plan* p, const void* w, void* out, const void* wt, void* psi, bool residual,
-                         long batch, void* ws, hipStream_t st) {
+                         long batch, void* ws, hipStream_t st, long ens_b0) {
     Ws<T> W = carve<T>(p, ws, batch);
     int rc;
     ColArgs<T> a{};
+    a.ens = ens_at<T>(p, ens_b0);
     a.planes = W.planes;
     a.plane_stride = W.plane_stride;
     a.u_in = (const cx<T>*)w;
@@ -2130,7 +2216,7 @@ static int step_vjp_impl(const tcfd_ns2d_plan* p, const void* saved, size_t save
         auto state = [&](int k) { return k == 0 ? u0 : (const cx<T>*)(V.u + (size_t)(k - 1) * V.stride); };
         auto from_u0 = [&](int k) { return k > 0 && base0 && base0[k]; };    // (at k = 0 the initial state IS the current one)
         for (int k = 0; k + 1 < nstages; ++k) {
-            if ((rc = explicit_impl<T, N>(p, state(k), V.F, nullptr, nullptr, false, batch, ws, st))) return rc;
+            if ((rc = explicit_impl<T, N>(p, state(k), V.F, nullptr, nullptr, false, batch, ws, st, 0))) return rc;
             hipLaunchKernelGGL(k_stage_update<T>, dim3(blocks), dim3(256), 0, st, (const cx<T>*)V.F,
                                k ? (const cx<T>*)V.hf[(k - 1) & 1] : nullptr, from_u0(k) ? u0 : state(k), lin, c(fa, k, 1),
                                (T)beta[k], (T)gdt[k], (T)mu[k], c(mud, k, mu[k]), V.hf[k & 1],
@@ -2196,16 +2282,16 @@ int fill_round_fields(tcfd_ns2d_plan* p) {
 template <typename T>
 int step(const tcfd_ns2d_plan* p, const void* w_in, void* w_out, void* dwdt, long batch, int nstages, const double* beta,
          const double* gdt, const double* mu_num, const double* fa, const double* mu_den, const int* base0, int steps,
-         double inv_total_dt, void* ws, hipStream_t st) {
+         double inv_total_dt, void* ws, hipStream_t st, long ens_b0) {
     return by_size(p->n, [&](auto N) {
         return step_impl<T, N()>(p, w_in, w_out, dwdt, batch, nstages, beta, gdt, mu_num, fa, mu_den, base0, steps, inv_total_dt,
-                                 ws, st);
+                                 ws, st, ens_b0);
     });
 }
 template <typename T>
 int explicit_terms(const tcfd_ns2d_plan* p, const void* w, void* out, const void* wt, void* psi, bool residual, long batch,
-                   void* ws, hipStream_t st) {
-    return by_size(p->n, [&](auto N) { return explicit_impl<T, N()>(p, w, out, wt, psi, residual, batch, ws, st); });
+                   void* ws, hipStream_t st, long ens_b0) {
+    return by_size(p->n, [&](auto N) { return explicit_impl<T, N()>(p, w, out, wt, psi, residual, batch, ws, st, ens_b0); });
 }
 template <typename T>
 int explicit_vjp(const tcfd_ns2d_plan* p, const void* w, const void* gm, void* xout, size_t x_field_stride, long batch, void* ws,

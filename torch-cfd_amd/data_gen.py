@@ -71,15 +71,19 @@ def generate_mcwilliams_dataset(n: int, total_samples: int, batch_size: int, dt:
     0's batches -- with nobody to receive from: the one-GPU PROXY of the N-GPU job's wall time that ``bench.py`` reports
     (the rows of the other ranks stay uninitialised; what the proxy leaves out is the receive + D2H of their records on the
     side streams)."""
-    def make_operator(grid):
-        return NavierStokes2DSpectral(viscosity=viscosity, grid=grid, drag=0, smooth=True, forcing_fn=None,
+    members = _per_sample_values(total_samples, viscosity=viscosity)
+
+    def make_operator(grid, start=0, count=None):
+        nu = viscosity if not members else members["viscosity"][start:start + count].tolist()
+        return NavierStokes2DSpectral(viscosity=nu, grid=grid, drag=0, smooth=True, forcing_fn=None,
                                       solver=RK4CrankNicolsonStepper())
 
     def initial_vorticity(grid, start, count, device):
         return vorticity_field(grid, peak_wavenumber, batch_seeds=[random_state + start + k for k in range(count)], device=device)
 
     return _generate_dataset(n, total_samples, batch_size, dt, warmup_steps, total_steps, record_every_steps, make_operator,
-                             initial_vorticity, diam, random_state, subsample, dtype, cdtype, device, dst, path, stats, as_rank0_of)
+                             initial_vorticity, diam, random_state, subsample, dtype, cdtype, device, dst, path, stats, as_rank0_of,
+                             members=members)
 
 
 def generate_kolmogorov_dataset(n: int, total_samples: int, batch_size: int, dt: float, warmup_steps: int,
@@ -103,17 +107,41 @@ def generate_kolmogorov_dataset(n: int, total_samples: int, batch_size: int, dt:
     from .forcings import KolmogorovForcing
     from .initial_conditions import curl_2d, filtered_velocity_field
 
-    def make_operator(grid):
-        forcing = KolmogorovForcing(grid=grid, scale=scale, wave_number=peak_wavenumber, swap_xy=False)
-        return NavierStokes2DSpectral(viscosity=viscosity, grid=grid, drag=drag, smooth=True, forcing_fn=forcing,
-                                      solver=RK4CrankNicolsonStepper())
+    members = _per_sample_values(total_samples, viscosity=viscosity, drag=drag, scale=scale)
+
+    def make_operator(grid, start=0, count=None):
+        def member(name, value):   # the slice of the batch's global sample indices, or the one value
+            return members[name][start:start + count].tolist() if name in members else value
+
+        per_sample_scale = "scale" in members   # then the forcing is sampled at amplitude 1 and scaled per member
+        forcing = KolmogorovForcing(grid=grid, scale=1.0 if per_sample_scale else scale, wave_number=peak_wavenumber,
+                                    swap_xy=False)
+        extra = {"forcing_scale": member("scale", scale)} if per_sample_scale else {}
+        return NavierStokes2DSpectral(viscosity=member("viscosity", viscosity), grid=grid, drag=member("drag", drag), smooth=True,
+                                      forcing_fn=forcing, solver=RK4CrankNicolsonStepper(), **extra)
 
     def initial_vorticity(grid, start, count, device):
         seeds = [random_state + g // batch_size + g % batch_size for g in range(start, start + count)]
         return curl_2d(filtered_velocity_field(grid, max_velocity, peak_wavenumber, batch_seeds=seeds, device=device), grid)
 
     return _generate_dataset(n, total_samples, batch_size, dt, warmup_steps, total_steps, record_every_steps, make_operator,
-                             initial_vorticity, diam, random_state, subsample, dtype, cdtype, device, dst, path, stats, as_rank0_of)
+                             initial_vorticity, diam, random_state, subsample, dtype, cdtype, device, dst, path, stats, as_rank0_of,
+                             members=members)
+
+
+def _per_sample_values(total_samples: int, **named) -> Dict[str, torch.Tensor]:
+    """The arguments given as SEQUENCES (one value per sample of the data set, by global sample index) as float64 tensors of
+    length ``total_samples``; single values are left out.  Empty: a data set of one physics, generated as it always was."""
+    out = {}
+    for name, value in named.items():
+        if value is None or isinstance(value, (int, float)) or (torch.is_tensor(value) and value.dim() == 0):
+            continue
+        t = torch.as_tensor(value, dtype=torch.float64).detach().reshape(-1).cpu()
+        if t.numel() != total_samples:
+            raise ValueError(f"{name}: a per-sample sequence needs one value per sample: {t.numel()} values for "
+                             f"total_samples = {total_samples}")
+        out[name] = t
+    return out
 
 
 def fno_sample_seeds(random_state: int, start: int, count: int) -> list:
@@ -179,11 +207,15 @@ def _generate_dataset(n: int, total_samples: int, batch_size: int, dt: float, wa
                       record_every_steps: int, make_operator, initial_vorticity, diam: float, random_state: int,
                       subsample: int, dtype: torch.dtype, cdtype: torch.dtype, device, dst: int, path: Optional[str],
                       stats: Optional[dict], as_rank0_of: Optional[int],
-                      spectral_initial_condition: bool = False) -> Optional[Dict[str, torch.Tensor]]:
+                      spectral_initial_condition: bool = False,
+                      members: Optional[Dict[str, torch.Tensor]] = None) -> Optional[Dict[str, torch.Tensor]]:
     """The batch loop the drivers share (fno/data_gen/data_gen_McWilliams2d.py:119-171, data_gen_Kolmogorov2d.py:134-192,
     data_gen_fno.py:188-252): ``make_operator(grid)`` builds the equation, ``initial_vorticity(grid, start, count, device)``
     the (count, n, n) physical initial vorticity of the samples with global indices start .. start + count - 1 -- or, with
-    ``spectral_initial_condition``, its (count, n, n/2 + 1) half spectrum, which then goes to the stepper as it is."""
+    ``spectral_initial_condition``, its (count, n, n/2 + 1) half spectrum, which then goes to the stepper as it is.
+    ``members`` (non-empty): per-sample parameters -- every batch steps on its own ensemble operator
+    ``make_operator(grid, start, count)``, built from the slice of the batch's global sample indices (so the split across ranks
+    does not change which sample gets which value), and the dict gains one entry per sequence."""
     import time
 
     import torch.distributed as dist
@@ -201,7 +233,7 @@ def _generate_dataset(n: int, total_samples: int, batch_size: int, dt: float, wa
             raise ValueError("as_rank0_of is the single-process proxy of a multi-rank job")
         layout = [batch_layout(total_samples, as_rank0_of, batch_size)[0]]
     grid = Grid(shape=(n, n), domain=((0, diam), (0, diam)), device=device)
-    op = make_operator(grid).to(device)
+    op = None if members else make_operator(grid).to(device)
     real = torch.get_default_dtype()
     plan = fft_plan(n, torch.complex128 if real == torch.float64 else torch.complex64, device, diam)
     ns = n // subsample
@@ -213,13 +245,16 @@ def _generate_dataset(n: int, total_samples: int, batch_size: int, dt: float, wa
         # their upload), and it must not run beside the page-locking of the result -- that holds the process's memory-map
         # lock and makes every page fault of this thread wait (measured: the first record of the C4 job 0.14 s late)
         cplx = torch.complex128 if real == torch.float64 else torch.complex64
-        op._plan(torch.empty(0, n, n // 2 + 1, dtype=cplx, device=device))
+        if op is not None:   # (an ensemble operator is built per batch, below)
+            op._plan(torch.empty(0, n, n // 2 + 1, dtype=cplx, device=device))
         fft_plan(n, torch.promote_types(cdtype, torch.complex64), device)
     if on_gpu:
         torch.cuda.synchronize(device)
     t_setup = time.perf_counter()
     try:
         for start, count in layout[rank]:
+            if members:
+                op = make_operator(grid, start, count).to(device)
             w = initial_vorticity(grid, start, count, device)
             if not spectral_initial_condition:
                 w = plan.rfft2(w)
@@ -252,6 +287,8 @@ def _generate_dataset(n: int, total_samples: int, batch_size: int, dt: float, wa
         return None
     full = dict(full)
     full["random_states"] = torch.arange(random_state, random_state + total_samples, dtype=torch.int32)
+    for name, values in (members or {}).items():
+        full[name] = values.clone()
     if path is not None:
         torch.save(full, path)
     return full

@@ -22,6 +22,8 @@ as device tensor ops around the HIP transforms and their hand-written adjoints -
 node whose backward is the adjoint model of the fused step (``tcfd_ns2d_step_vjp``; ``adjoint_step`` is the same without
 autograd).  A forward-mode dual number
 (``torch.autograd.forward_ad``) as the state runs the tangent-linear kernels (``explicit_terms_jvp`` / ``tangent_step``).
+``viscosity`` / ``drag`` / ``forcing_scale`` given per sample make the operator an ENSEMBLE: field b of a call steps with member
+b's values in the same fused kernels (``tcfd_ns2d_plan_set_ensemble``), forward and reverse mode with respect to the state.
 """
 from __future__ import annotations
 
@@ -96,6 +98,27 @@ class _HipPlan:
         self.handle = handle
         self._ws: Optional[torch.Tensor] = None
         self._finalizer = weakref.finalize(self, self.lib.tcfd_ns2d_plan_destroy, handle)
+
+    def set_ensemble(self, laplace, nu, drag, forcing_scale):
+        """Per-sample physics (``tcfd_ns2d_plan_set_ensemble``): field b of every call steps with ``nu[b] * laplace - drag[b]``
+        and ``forcing_scale[b]`` times the plan's forcing.  ``nu`` / ``drag`` / ``forcing_scale``: sequences of one length;
+        an empty ``nu`` makes the plan scalar again."""
+        if not hasattr(self.lib, "tcfd_ns2d_plan_set_ensemble"):   # added without a new ABI number: a stale library loads, but lacks it
+            raise _lib.TcfdError(f"{_lib.LIB_PATH} was built before per-sample parameters (tcfd_ns2d_plan_set_ensemble) were "
+                                 "added: rebuild it with torch_cfd_amd._lib.build_library(force=True)")
+        count = len(nu)
+        if count == 0:
+            rc = self.lib.tcfd_ns2d_plan_set_ensemble(self.handle, 0, None, None, None, None)
+        else:
+            if len(drag) != count or len(forcing_scale) != count:
+                raise ValueError(f"set_ensemble: {count} viscosities, {len(drag)} drags, {len(forcing_scale)} forcing scales")
+            lap = laplace.detach().to("cpu", torch.float64).contiguous()
+            assert lap.shape == (self.n, self.m)
+            with torch.cuda.device(self.device):
+                rc = self.lib.tcfd_ns2d_plan_set_ensemble(self.handle, count, _lib.dptr_of_tensor(lap), _lib.darray(nu),
+                                                          _lib.darray(drag), _lib.darray(forcing_scale))
+        _lib.check(rc, "tcfd_ns2d_plan_set_ensemble")
+        self.ens_count = count
 
     def info(self) -> Dict[str, int]:
         a, b, c = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
@@ -543,6 +566,46 @@ class RK4CrankNicolsonStepper(IMEXStepper):
 
 
 # ----------------------------------------------------------------------------- the operator
+def _per_sample(value, name: str) -> Optional[torch.Tensor]:
+    """None for one value (a number, a 0-dim tensor), else the per-sample values as a 1-D float64 CPU tensor: a 1-D sequence
+    / array / tensor of length B, or a (B, 1, 1) tensor."""
+    if value is None or isinstance(value, (int, float)):
+        return None
+    if torch.is_tensor(value):
+        if value.dim() == 0:
+            return None
+        if value.requires_grad:
+            raise NotImplementedError(f"{name}: per-sample parameters are data -- a {name} that requires grad is not implemented "
+                                      "(gradients with respect to the parameters are out of scope); detach it")
+        t = value.detach()
+    else:
+        t = torch.as_tensor(value, dtype=torch.float64)
+        if t.dim() == 0:
+            return None
+    if not (t.dim() == 1 or (t.dim() == 3 and tuple(t.shape[1:]) == (1, 1))) or t.numel() == 0:
+        raise ValueError(f"{name}: per-sample values are a 1-D sequence of length B or a (B, 1, 1) tensor, got shape {tuple(t.shape)}")
+    return t.reshape(-1).to("cpu", torch.float64)
+
+
+def _ensemble_members(viscosity, drag, forcing_scale):
+    """None when every argument is one value (the scalar operator), else the three per-sample value vectors (float64, CPU, one
+    length; single values repeated, a missing forcing scale = 1)."""
+    given = {"viscosity": _per_sample(viscosity, "viscosity"), "drag": _per_sample(drag, "drag"),
+             "forcing_scale": _per_sample(forcing_scale, "forcing_scale")}
+    sizes = {k: int(v.numel()) for k, v in given.items() if v is not None}
+    if not sizes:
+        return None
+    if len(set(sizes.values())) != 1:
+        raise ValueError("per-sample parameters of different lengths: " + ", ".join(f"{k} has {v}" for k, v in sizes.items()))
+    count = next(iter(sizes.values()))
+    for name, single in (("viscosity", viscosity), ("drag", drag), ("forcing_scale", forcing_scale)):
+        if given[name] is None:
+            if torch.is_tensor(single) and single.requires_grad:
+                raise NotImplementedError(f"{name}: per-sample parameters are data -- a {name} that requires grad is not implemented")
+            given[name] = torch.full((count,), 1.0 if single is None else float(single), dtype=torch.float64)
+    return given["viscosity"], given["drag"], given["forcing_scale"]
+
+
 class NavierStokes2DSpectral(ImplicitExplicitODE):
     """2-D vorticity equation on a periodic box, pseudo-spectral:
 
@@ -559,23 +622,70 @@ class NavierStokes2DSpectral(ImplicitExplicitODE):
     #: INTEGRATION.md.
     forcing_noise_floor: Optional[float] = None
 
-    def __init__(self, viscosity: float, grid: Grid, drag: float = 0.0, smooth: bool = True,
-                 forcing_fn: Optional[Callable] = None, solver: IMEXStepper = None, **kwargs):
+    def __init__(self, viscosity, grid: Grid, drag=0.0, smooth: bool = True,
+                 forcing_fn: Optional[Callable] = None, solver: IMEXStepper = None, forcing_scale=None, **kwargs):
+        """``viscosity`` / ``drag``: a float -- one physics for every field, as the reference -- or per-sample values: a 1-D
+        sequence / tensor of length B or a (B, 1, 1) tensor (the reference's broadcasting form).  ``forcing_scale``: a float or
+        a length-B sequence; sample b is forced by ``forcing_scale[b] * f``.  Any per-sample argument makes the operator an
+        ENSEMBLE of B members: field b of a (B, n, m) or (B, T, n, m) state steps with member b's values."""
         super().__init__()
-        self.viscosity, self.grid, self.drag, self.smooth = viscosity, grid, drag, smooth
+        self.grid, self.smooth = grid, smooth
+        members = _ensemble_members(viscosity, drag, forcing_scale)
+        self._ens_count = 0 if members is None else int(members[0].numel())
+        if members is None:   # the scalar operator: attributes, buffers and plan as they always were
+            self.viscosity, self.drag, self.forcing_scale = viscosity, drag, forcing_scale
         self.forcing_fn = forcing_fn
         self.solver = solver
         self._plans: Dict[tuple, _HipPlan] = {}
         self._coef_cache = None
-        self._initialize()
+        self._initialize(members)
 
-    def _initialize(self):
+    def _initialize(self, members=None):
         kx, ky = self.grid.rfft_mesh()
         laplace = -4 * torch.pi**2 * (abs(kx) ** 2 + abs(ky) ** 2)
-        for name, table in (("kx", kx), ("ky", ky), ("laplace", laplace),
-                            ("linear_term", self.viscosity * laplace - self.drag),
-                            ("filter", brick_wall_filter_2d(self.grid))):
+        if members is None:
+            tables = (("linear_term", self.viscosity * laplace - self.drag),)
+        else:
+            # per-sample BUFFERS in the reference's broadcasting shape and the tables' precision; no resident (B, n, m) linear term
+            # (269 MB at 1024^2 x 64 in fp64): the kernels form it per field, the `linear_term` attribute on request
+            tables = tuple((name, v.to(laplace.dtype).reshape(-1, 1, 1))
+                           for name, v in zip(("viscosity", "drag", "forcing_scale"), members))
+        for name, table in (("kx", kx), ("ky", ky), ("laplace", laplace)) + tables + (("filter", brick_wall_filter_2d(self.grid)),):
             self.register_buffer(name, table)
+
+    def __getattr__(self, name):
+        if name == "linear_term" and self.__dict__.get("_ens_count"):
+            # an ensemble keeps no table: the reference's (B, n, m) value, evaluated when asked for
+            return self.viscosity * self.laplace - self.drag
+        return super().__getattr__(name)
+
+    # -- per-sample parameters
+    _ENS_LIMIT = ("{what} is not implemented for an operator with per-sample parameters (viscosity / drag / forcing_scale given "
+                  "per sample): the tangent-linear and adjoint kernels read one linear-term table -- run one scalar operator per "
+                  "member, or differentiate forward() in reverse mode")
+
+    def _refuse_ensemble(self, what: str):
+        if self._ens_count:
+            raise NotImplementedError(self._ENS_LIMIT.format(what=what))
+
+    def _ens_slices(self, w, what: str = "state") -> int:
+        """T of a (B, T, n, m) ``w`` on an ensemble of B members (1 for (B, n, m)); any other leading size raises."""
+        if not torch.is_tensor(w) or w.dim() not in (3, 4) or w.shape[0] != self._ens_count:
+            lead = tuple(w.shape[:-2]) if torch.is_tensor(w) else None
+            raise ValueError(f"{what}: this operator has per-sample parameters for B = {self._ens_count} members and takes a "
+                             f"(B, n, m) or (B, T, n, m) half spectrum whose field b belongs to member b; got leading size {lead}")
+        return 1 if w.dim() == 3 else int(w.shape[1])
+
+    def _member_rows(self, buf: torch.Tensor, w3: torch.Tensor) -> torch.Tensor:
+        """The (B, 1, 1) per-sample buffer ``buf`` as one row per field of the flattened (B * T, n, m) state ``w3``."""
+        return buf.to(w3.device).repeat_interleave(w3.shape[0] // self._ens_count, dim=0)
+
+    def _lin_like(self, w: torch.Tensor) -> torch.Tensor:
+        if not self._ens_count:
+            return self.linear_term
+        self._ens_slices(w)
+        lin = self.linear_term
+        return lin if w.dim() == 3 else lin.unsqueeze(1)
 
     def __getstate__(self):  # device plans are rebuilt lazily after copy / unpickle
         state = self.__dict__.copy()
@@ -610,6 +720,8 @@ class NavierStokes2DSpectral(ImplicitExplicitODE):
         if scale > 0:
             mag = fh.abs()
             fh = torch.where(mag > scale * torch.finfo(real).eps * mag.max(), fh, torch.zeros_like(fh))
+        if not self._ens_count and self.forcing_scale is not None:   # one amplitude for every field
+            fh = fh * float(self.forcing_scale)
         return fh
 
     def _forcing_key(self):
@@ -625,9 +737,11 @@ class NavierStokes2DSpectral(ImplicitExplicitODE):
         self._plans, self._coef_cache = {}, None
 
     def _plan(self, like: torch.Tensor) -> _HipPlan:
+        if self._ens_count:
+            return self._ensemble_plan(like)
         cdtype = torch.promote_types(like.dtype, _COMPLEX_OF.get(self.linear_term.dtype, torch.complex64))
         tables = (self.kx, self.ky, self.linear_term, self.filter)
-        key = (cdtype, like.device, self.smooth, self._forcing_key(), self.forcing_noise_floor) + tuple(
+        key = (cdtype, like.device, self.smooth, self._forcing_key(), self.forcing_noise_floor, self.forcing_scale) + tuple(
             (t.data_ptr(), t._version) for t in tables)
         plan = self._plans.get(key)
         if plan is None:
@@ -644,16 +758,48 @@ class NavierStokes2DSpectral(ImplicitExplicitODE):
             self._plans = {key: plan}  # tables changed -> drop stale plans
         return plan
 
+    def _ensemble_plan(self, like: torch.Tensor) -> _HipPlan:
+        """The plan of an ensemble operator for the state ``like``: the scalar plan of member 0 (mask, forcing spectrum,
+        transforms), switched to per-sample physics.  A (B, T, n, m) state steps as B * T fields, member b's values T times."""
+        reps = self._ens_slices(like)
+        cdtype = torch.promote_types(like.dtype, _COMPLEX_OF.get(self.laplace.dtype, torch.complex64))
+        tables = (self.kx, self.ky, self.laplace, self.filter, self.viscosity, self.drag, self.forcing_scale)
+        for t in tables[-3:]:
+            if t.requires_grad:
+                raise NotImplementedError("per-sample parameters are data: a viscosity / drag / forcing_scale that requires grad is "
+                                          "not implemented (gradients with respect to the parameters are out of scope)")
+        key = (cdtype, like.device, self.smooth, self._forcing_key(), self.forcing_noise_floor) + tuple(
+            (t.data_ptr(), t._version) for t in tables)
+        plan = self._plans.get(key)
+        if plan is None:
+            n, m = self.kx.shape[-2:]
+            if self.grid.shape[0] != self.grid.shape[1] or n != self.grid.shape[0]:
+                raise ValueError("the HIP spectral path needs a square n x n grid")
+            if not _is_pow2(n):
+                raise NotImplementedError(f"per-sample parameters run on the fused grid sizes only (n = 2^k in 8..4096, 3 * 2^k in "
+                                          f"96..1536, 5 * 2^k in 80..1280); n = {n} runs on the composite / dense plans, which step "
+                                          "one physics per call")
+            mask = self.filter if self.smooth else torch.ones_like(self.filter)
+            lin0 = self.viscosity[0] * self.laplace - self.drag[0]
+            plan = _HipPlan(n, cdtype, like.device, self.kx[:, 0], self.ky[0, :], lin0, mask, self.forcing_hat())
+            plan._ens_reps = 0
+            self._plans = {key: plan}
+        if plan._ens_reps != reps:
+            nu, drag, fs = (t.detach().reshape(-1).to("cpu", torch.float64).repeat_interleave(reps).tolist() for t in tables[-3:])
+            plan.set_ensemble(self.laplace, nu, drag, fs)
+            plan._ens_reps = reps
+        return plan
+
     # -- gradients: the differentiable form of the same arithmetic (autograd.py), only when somebody asks
     @staticmethod
     def _wants_grad(*tensors) -> bool:
         return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 
-    def _forcing_on(self, like: torch.Tensor):
+    def _forcing_on(self, like: torch.Tensor, plan=None):
         """The forcing spectrum on the device, sampled once per plan (the plan is rebuilt when the forcing's fingerprint or a
         table changes): sampling it again on every differentiable call cost a CPU rfft2 of the grid each time (30-50 ms at
         1024^2 -- more than the step)."""
-        plan = self._plan(like)
+        plan = self._plan(like) if plan is None else plan
         cached = getattr(plan, "_forcing_dev", None)
         if cached is None:
             fh = self.forcing_hat()
@@ -668,9 +814,12 @@ class NavierStokes2DSpectral(ImplicitExplicitODE):
         w = vort_hat.to(plan.cdtype)
         lead = w.shape
         w = w.reshape(-1, plan.n, plan.m)
-        forcing = self._forcing_on(w)
+        forcing = self._forcing_on(w, plan)
+        if self._ens_count and forcing is not None:   # member b's forcing, one row per field
+            forcing = self._member_rows(self.forcing_scale, w).to(forcing.real.dtype) * forcing
         constant = not any(torch.is_tensor(v) and v.requires_grad for v in params.values())
-        if (constant and ad._fused_vjp_ok(plan) and _is_module_stepper(stepper) and os.environ.get("TCFD_FUSED_STAGE", "1") != "0"
+        # (an ensemble never takes the fused-stage nodes or the one-node adjoint: their kernels read one table)
+        if (constant and not self._ens_count and ad._fused_vjp_ok(plan) and _is_module_stepper(stepper) and os.environ.get("TCFD_FUSED_STAGE", "1") != "0"
                 and w.is_cuda):
             # only the STATE asks for gradients: the schedule is plain numbers (rounded as the fused forward kernels round them)
             if ad._fused_adjoint_ok(plan) and steps >= 1:
@@ -700,6 +849,7 @@ class NavierStokes2DSpectral(ImplicitExplicitODE):
     def _jvp_plan(self, w_hat, dw_hat, what: str, dual: str = "tangent", kernels: str = "tangent-linear") -> _HipPlan:
         """Checks shared by the tangent-linear entry points and the adjoint model (``dual`` = "cotangent"), in the order shapes
         (ValueError) -> gradients -> device plan."""
+        self._refuse_ensemble(what)
         if not (torch.is_tensor(w_hat) and torch.is_tensor(dw_hat)) or w_hat.shape != dw_hat.shape or w_hat.dtype != dw_hat.dtype:
             raise ValueError(f"{what}: the {dual} must have the shape and dtype of the state, got "
                              f"{tuple(getattr(dw_hat, 'shape', ()))} {getattr(dw_hat, 'dtype', None)} for "
@@ -796,6 +946,7 @@ class NavierStokes2DSpectral(ImplicitExplicitODE):
         params = stepper.params if params is None else params
         primal, tangent = fwAD.unpack_dual(vort_hat)
         if tangent is not None:   # forward-mode dual number: the tangent-linear step carries it
+            self._refuse_ensemble("a forward-mode dual number as the state (tangent_step)")
             out, dout = self._tangent_steps(primal, tangent, dt, steps, params, stepper)
             new = fwAD.make_dual(out, dout)
             if not want_dwdt:
@@ -813,25 +964,31 @@ class NavierStokes2DSpectral(ImplicitExplicitODE):
     def explicit_terms(self, vort_hat):
         primal, tangent = fwAD.unpack_dual(vort_hat)
         if tangent is not None:
+            self._refuse_ensemble("a forward-mode dual number as the state (explicit_terms_jvp)")
             return fwAD.make_dual(*self.explicit_terms_jvp(primal, tangent))
         if self._wants_grad(vort_hat):
             from . import autograd as ad
 
             plan = self._plan(vort_hat)
             w = vort_hat.to(plan.cdtype).reshape(-1, plan.n, plan.m)
-            return ad.explicit_terms(self, plan, w, self._forcing_on(w)).reshape(vort_hat.shape)
+            forcing = self._forcing_on(w, plan)
+            if self._ens_count and forcing is not None:
+                forcing = self._member_rows(self.forcing_scale, w).to(forcing.real.dtype) * forcing
+            return ad.explicit_terms(self, plan, w, forcing).reshape(vort_hat.shape)
         return self._plan(vort_hat).explicit_terms(vort_hat).reshape(vort_hat.shape)
 
     _explicit_terms = explicit_terms
 
     def implicit_terms(self, vort_hat):
-        return self.linear_term * vort_hat
+        return self._lin_like(vort_hat) * vort_hat
 
     def implicit_solve(self, vort_hat, dt):
-        return vort_hat / (1 - dt * self.linear_term)
+        return vort_hat / (1 - dt * self._lin_like(vort_hat))
 
     def residual(self, vhat: torch.Tensor, vt_hat: torch.Tensor):
         dual = any(fwAD.unpack_dual(t).tangent is not None for t in (vhat, vt_hat))   # forward mode: through explicit_terms
+        if dual:
+            self._refuse_ensemble("a forward-mode dual number in residual")
         if dual or self._wants_grad(vhat, vt_hat):
             return vt_hat - self.explicit_terms(vhat) - self.implicit_terms(vhat)
         _, res = self._plan(vhat).stream_residual(vhat, vt_hat, want_psi=False)

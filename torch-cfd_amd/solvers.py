@@ -44,7 +44,8 @@ def get_trajectory_imex(
     the stacks on the device (used by the multi-GPU gather).  With a ``record_sink`` nothing is stacked: every
     record goes to ``record_sink(index, {name: (*, n, m) complex dtype})`` as soon as it exists (device tensors on the
     current stream) and the function returns ``{}`` -- the ensemble driver post-processes and hands records over while
-    the following steps run (``data_gen.py``, ``distributed.RecordHandover``)."""
+    the following steps run (``data_gen.py``, ``distributed.RecordHandover``).  An ensemble operator (per-sample viscosity /
+    drag / forcing amplitude) records like any other: sample b of ``w0`` is member b in every record."""
     # require_grad: the reference marks w / dw/dt of every step as requiring grad and records DETACHED copies
     # (solvers.py:224-250); here the steps then run through the differentiable path (torch-cfd_amd/autograd.py)
     if require_grad:
