@@ -696,6 +696,23 @@ int tcfd_fvm_step_vjp(const tcfd_fvm_plan* plan, const void* saved, const void* 
  * itself in tcfd_last_error.  A plan without the flag (a fresh plan; on = 0) behaves as before this entry point existed. */
 int tcfd_fvm_plan_set_tangent(tcfd_fvm_plan* plan, int on);
 
+/* Per-sample physics of a finite-volume plan (an ENSEMBLE of `count` members): field b of every call that evaluates the explicit
+ * terms, their tangent or their adjoint (explicit_terms, step, explicit_terms_vjp, step_vjp) runs with nu_over_density[b],
+ * drag[b] (applied where drag[b] > 0, as the plan's scalar is) and the plan's forcing times forcing_scale[b] (the product
+ * rounded to the field precision, then added where the forcing is added; the tangent and the adjoint carry no forcing).  The
+ * host doubles are copied into a plan-owned device table in the field precision, converted as the plan's scalars are, so member
+ * b is bit-equal to a scalar plan of (nu_over_density[b], drag[b]) on field b alone when its forcing scale is 1.
+ *   drag == NULL: every member takes the plan's scalar drag;  forcing_scale == NULL: a scale of 1.
+ *   count == 0 clears the table (the pointers are not read): the plan is scalar again, with the bits it had.
+ * Such a plan takes batch == count, a tangent plan batch == 2 * count (field b and field count + b both use member b); any
+ * other batch returns TCFD_EINVAL and names both numbers.  tcfd_fvm_project reads no physics and takes any batch.
+ * TCFD_EINVAL before any device call: a null plan, count < 0, count > 0 without nu_over_density, forcing scales on a plan
+ * created without forcing.  The table is set whole or not at all: after a failure the plan is as it was.  The call waits for
+ * the device before it frees an earlier table; it takes no workspace.  Added under revision 13 without a new number, like
+ * tcfd_fvm_plan_set_tangent: a plan keeps its behaviour until the call sets a table. */
+int tcfd_fvm_plan_set_ensemble(tcfd_fvm_plan* plan, long count, const double* nu_over_density, const double* drag,
+                               const double* forcing_scale);
+
 /* ---- Gaussian random field: half spectrum of the (sub-sampled) sample, no transform -------------------------------
  * Replaces GRF2d.sample of fno/data_gen/grf.py:79-115 followed by the driver's nearest sub-sampling and rfft2
  * (fno/data_gen/data_gen_fno.py:195-205).  The reference takes s = Re(ifft2(sqrt_eig * c)) on an n0 x n0 mesh, keeps every

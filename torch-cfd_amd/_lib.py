@@ -229,6 +229,7 @@ SIGNATURES = {
     "tcfd_fvm_plan_destroy": (None, [_vp]),
     "tcfd_fvm_plan_set_advection": (_i, [_vp, _i]),
     "tcfd_fvm_plan_set_tangent": (_i, [_vp, _i]),
+    "tcfd_fvm_plan_set_ensemble": (_i, [_vp, _l, _dp, _dp, _dp]),
     "tcfd_fvm_workspace_bytes": (_sz, [_vp, _l]),
     "tcfd_fvm_explicit_terms": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _d, _vp]),
     "tcfd_fvm_project": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _vp, _sz, _vp]),

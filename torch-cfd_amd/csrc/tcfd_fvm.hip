@@ -24,6 +24,10 @@
 // state kernel's own code and dk = J_F(u) du from the same stencil, and writes the RK targets of both halves.  Every other pass
 // (k_fvm_div, the transforms, k_fvm_mul, k_fvm_apply) is linear per field and runs unchanged over the 2 B fields.
 //
+// Ensemble plan (tcfd_fvm_plan_set_ensemble): sample b of a call runs with its own viscosity, drag and forcing amplitude.  The three
+// stage kernels (k_fvm_stage, k_fvm_stage_jvp, k_fvm_stage_vjp) have an EnsConst instantiation that reads the three values of
+// member blockIdx.z from a plan-owned table; every other pass reads no physics and runs unchanged.
+//
 // Every arithmetic expression restates the reference's operation order; floating-point contraction is off in this file
 // so that a * b + c rounds twice as the reference's tensor ops do.
 #include <hip/hip_runtime.h>
@@ -52,6 +56,54 @@ struct StageConst {
     T h;
     int drag_on;
 };
+
+// Per-sample physics (tcfd_fvm_plan_set_ensemble): the constants of ONE member of an ensemble plan.  The plan owns a device table
+// of count x {nu / density, -drag, forcing_scale} in the field type; a workgroup belongs to one sample (blockIdx.z), so the three
+// values are workgroup-uniform loads and nothing is loaded per lane.  The device functions below are templates on the type of
+// their constants, S: StageConst<T> is the scalar plan's and compiles to the code it always did, MemberConst<T> the ensemble's.
+template <typename T>
+struct MemberConst : StageConst<T> {
+    T fscale;   // the member's forcing is fl(fscale * f), then added where f is added (1: today's sum)
+};
+template <typename S>
+constexpr bool kScaledForcing = false;
+template <typename T>
+constexpr bool kScaledForcing<MemberConst<T>> = true;
+
+constexpr int ENS_ROW = 3;   // values per member in the table
+
+// The stage kernels are templates on the type S of their constants ARGUMENT.  S = StageConst<T> is the scalar plan's kernel: its
+// argument list is what it was before per-sample physics existed, and so are the registers, scratch and occupancy of all 24
+// instantiations (profiles/fvm_ensemble_kernel_resource_usage.txt).  S = EnsConst<T> is the ensemble plan's: the plan's
+// constants and its member table, of which sample blockIdx.z reads row blockIdx.z.  The choice is made at compile time
+// (if constexpr (kEnsemble<S>)); no kernel branches on a table at run time.  Keep the kernel bodies in the __global__
+// functions: moving them into a shared inlined function changed the scalar kernels' register allocation (same file).
+template <typename T>
+struct EnsConst {
+    StageConst<T> plan;
+    const T* rows;   // ENS_ROW values per member; row 0 belongs to sample 0 of the launch
+};
+template <typename S>
+constexpr bool kEnsemble = false;
+template <typename T>
+constexpr bool kEnsemble<EnsConst<T>> = true;
+
+// the constants of member `b`: the plan's, with the member's nu, -drag and forcing scale.  drag_on is per member; -drag is
+// exact in the field type up to underflow, where a drag that rounds to zero adds a zero.
+template <typename T>
+__device__ __forceinline__ MemberConst<T> member_const(const StageConst<T>& s, const T* __restrict__ ens, unsigned b) {
+    const T* m = ens + (size_t)ENS_ROW * b;
+    MemberConst<T> r;
+    r.cfl = s.cfl;
+    r.inv_h2 = s.inv_h2;
+    r.sum_s = s.sum_s;
+    r.h = s.h;
+    r.nu = m[0];
+    r.neg_drag = m[1];
+    r.drag_on = m[1] < T(0);
+    r.fscale = m[2];
+    return r;
+}
 
 constexpr int MAXT = 4;   // stages of an explicit tableau (and so RK targets of one stage: the later stages + the final sum)
 
@@ -123,10 +175,9 @@ struct Near {
 };
 
 // ((convect + nu lap) + f) + (-drag) u from the advection terms of cell (i, j) (fvm.py:397-409)
-template <typename T>
+template <typename T, typename S>
 __device__ __forceinline__ void finish_point(const Near<T>& v, T adv_x, T adv_y, const T* __restrict__ fx,
-                                             const T* __restrict__ fy, int i, int j, int n, const StageConst<T>& s, T& kx,
-                                             T& ky) {
+                                             const T* __restrict__ fy, int i, int j, int n, const S& s, T& kx, T& ky) {
     // laplacian (finite_differences.py:150): (-2 u) * sum(scales) + (u[-1] + u[+1]) * s0 + (u[-1] + u[+1]) * s1
     T lap_x = (T(-2) * v.x00) * s.sum_s;
     lap_x = lap_x + (v.xm1 + v.xp1) * s.inv_h2;
@@ -139,8 +190,13 @@ __device__ __forceinline__ void finish_point(const Near<T>& v, T adv_x, T adv_y,
     ky = adv_y + s.nu * lap_y;
     if (fx) {
         const size_t p = (size_t)i * n + j;
-        kx = kx + fx[p];
-        ky = ky + fy[p];
+        if constexpr (kScaledForcing<S>) {
+            kx = kx + s.fscale * fx[p];
+            ky = ky + s.fscale * fy[p];
+        } else {
+            kx = kx + fx[p];
+            ky = ky + fy[p];
+        }
     }
     if (s.drag_on) {
         kx = kx + v.x00 * s.neg_drag;
@@ -151,9 +207,9 @@ __device__ __forceinline__ void finish_point(const Near<T>& v, T adv_x, T adv_y,
 // explicit_terms of both velocity components at cell (i, j) of field plane X / Y, the advection by the scheme SCHEME.
 // VAN_LEER reads the -2 .. +2 stencils of both components and two corners, 20 loads; the two-cell schemes the 5-point
 // stencils and the same corners, 12 loads: their branch never forms the +-2 indices.
-template <int SCHEME, typename T>
+template <int SCHEME, typename T, typename S>
 __device__ __forceinline__ void explicit_point(const T* __restrict__ X, const T* __restrict__ Y, const T* __restrict__ fx,
-                                               const T* __restrict__ fy, int i, int j, int n, const StageConst<T>& s,
+                                               const T* __restrict__ fy, int i, int j, int n, const S& s,
                                                T& kx, T& ky) {
     auto at = [n](const T* p, int a, int b) { return p[(size_t)a * n + b]; };
     if constexpr (SCHEME == VAN_LEER) {
@@ -215,18 +271,20 @@ __device__ __forceinline__ void explicit_point(const T* __restrict__ X, const T*
 }
 
 // one thread per cell; blockIdx.z = sample
-template <int SCHEME, typename T>
+template <int SCHEME, typename T, typename S>
 __global__ void __launch_bounds__(256) k_fvm_stage(const T* __restrict__ ux, const T* __restrict__ uy, const T* __restrict__ u0x,
                                                    const T* __restrict__ u0y, const T* __restrict__ fx, const T* __restrict__ fy,
-                                                   T* __restrict__ kx_out, T* __restrict__ ky_out, Targets<T> tg, StageConst<T> s,
-                                                   int n) {
+                                                   T* __restrict__ kx_out, T* __restrict__ ky_out, Targets<T> tg, S s, int n) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     const int i = blockIdx.y * blockDim.y + threadIdx.y;
     if (i >= n || j >= n) return;
     const size_t plane = (size_t)n * n;
     const size_t base = (size_t)blockIdx.z * plane;
     T kx, ky;
-    explicit_point<SCHEME>(ux + base, uy + base, fx, fy, i, j, n, s, kx, ky);
+    if constexpr (kEnsemble<S>)
+        explicit_point<SCHEME>(ux + base, uy + base, fx, fy, i, j, n, member_const(s.plan, s.rows, blockIdx.z), kx, ky);
+    else
+        explicit_point<SCHEME>(ux + base, uy + base, fx, fy, i, j, n, s, kx, ky);
     const size_t p = base + (size_t)i * n + j;
     if (kx_out) {
         kx_out[p] = kx;
@@ -312,9 +370,9 @@ __device__ __forceinline__ T face_flux_jvp(T c0, T c1, T w, T dc0, T dc1, T dw, 
 // the perturbation, and the forcing, which does not depend on the state, drops out.  The state loads repeat the addresses
 // explicit_point reads, so next to it in one kernel they are loaded once.  As there, the two-cell schemes never form the +-2
 // addresses, of X and Y or of DX and DY.
-template <int SCHEME, typename T>
+template <int SCHEME, typename T, typename S>
 __device__ __forceinline__ void explicit_point_jvp(const T* __restrict__ X, const T* __restrict__ Y, const T* __restrict__ DX,
-                                                   const T* __restrict__ DY, int i, int j, int n, const StageConst<T>& s, T& dkx,
+                                                   const T* __restrict__ DY, int i, int j, int n, const S& s, T& dkx,
                                                    T& dky) {
     auto at = [n](const T* p, int a, int b) { return p[(size_t)a * n + b]; };
     const int im1 = wrap(i - 1, n), ip1 = wrap(i + 1, n);
@@ -373,19 +431,25 @@ __device__ __forceinline__ void explicit_point_jvp(const T* __restrict__ X, cons
 // apart.  One thread per cell of the B samples; blockIdx.z = sample.  The state half is k_fvm_stage's own code (explicit_point,
 // the same target expressions), so it is bit-equal to the plain kernel; the tangent half writes (du0, dk) to the same targets
 // with the same modes and weights.
-template <int SCHEME, typename T>
+template <int SCHEME, typename T, typename S>
 __global__ void __launch_bounds__(256) k_fvm_stage_jvp(const T* __restrict__ ux, const T* __restrict__ uy, const T* __restrict__ u0x,
                                                        const T* __restrict__ u0y, const T* __restrict__ fx, const T* __restrict__ fy,
-                                                       T* __restrict__ kx_out, T* __restrict__ ky_out, Targets<T> tg, StageConst<T> s,
-                                                       int n, size_t pair) {
+                                                       T* __restrict__ kx_out, T* __restrict__ ky_out, Targets<T> tg, S s, int n,
+                                                       size_t pair) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     const int i = blockIdx.y * blockDim.y + threadIdx.y;
     if (i >= n || j >= n) return;
     const size_t plane = (size_t)n * n;
     const size_t base = (size_t)blockIdx.z * plane;
     T kx, ky, dkx, dky;
-    explicit_point<SCHEME>(ux + base, uy + base, fx, fy, i, j, n, s, kx, ky);
-    explicit_point_jvp<SCHEME>(ux + base, uy + base, ux + pair + base, uy + pair + base, i, j, n, s, dkx, dky);
+    if constexpr (kEnsemble<S>) {   // the state field b and its perturbation, field B + b, both step with member b = blockIdx.z
+        const MemberConst<T> m = member_const(s.plan, s.rows, blockIdx.z);
+        explicit_point<SCHEME>(ux + base, uy + base, fx, fy, i, j, n, m, kx, ky);
+        explicit_point_jvp<SCHEME>(ux + base, uy + base, ux + pair + base, uy + pair + base, i, j, n, m, dkx, dky);
+    } else {
+        explicit_point<SCHEME>(ux + base, uy + base, fx, fy, i, j, n, s, kx, ky);
+        explicit_point_jvp<SCHEME>(ux + base, uy + base, ux + pair + base, uy + pair + base, i, j, n, s, dkx, dky);
+    }
     const size_t p = base + (size_t)i * n + j;
     const size_t dp = pair + p;
     if (kx_out) {
@@ -573,9 +637,9 @@ __device__ __forceinline__ FaceBar<T> face_flux_vjp(T c0, T c1, T w, T cfl, T la
 // Y[i][j] likewise.  The faces two cells away have identically zero partials and are not evaluated: 10 flux evaluations per
 // cell (FY[i][j] and GX[i][j] serve both components), reading the 5-point stencils of X and Y, the corners (i-1, j+1) and
 // (i+1, j-1) of both, the 5-point stencils of LX and LY, LX[i-1][j+1] and LY[i+1][j-1].
-template <int SCHEME, typename T>
+template <int SCHEME, typename T, typename S>
 __device__ __forceinline__ void explicit_point_vjp(const T* __restrict__ X, const T* __restrict__ Y, const T* __restrict__ LX,
-                                                   const T* __restrict__ LY, int i, int j, int n, const StageConst<T>& s, T& lx,
+                                                   const T* __restrict__ LY, int i, int j, int n, const S& s, T& lx,
                                                    T& ly) {
     auto at = [n](const T* p, int a, int b) { return p[(size_t)wrap(a, n) * n + wrap(b, n)]; };
     auto cot = [&](const T* l, int a, int b, int a1, int b1) { return (at(l, a1, b1) - at(l, a, b)) / s.h; };
@@ -685,16 +749,19 @@ __device__ __forceinline__ void explicit_point_vjp(const T* __restrict__ X, cons
 }
 
 // (ox, oy) = J_F(u)^T (lx, ly), or += with accumulate (stage 0 of the reverse step adds straight into the cotangent of u0)
-template <int SCHEME, typename T>
+template <int SCHEME, typename T, typename S>
 __global__ void __launch_bounds__(256) k_fvm_stage_vjp(const T* __restrict__ ux, const T* __restrict__ uy, const T* __restrict__ lx,
                                                        const T* __restrict__ ly, T* __restrict__ ox, T* __restrict__ oy,
-                                                       int accumulate, StageConst<T> s, int n) {
+                                                       int accumulate, S s, int n) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     const int i = blockIdx.y * blockDim.y + threadIdx.y;
     if (i >= n || j >= n) return;
     const size_t base = (size_t)blockIdx.z * n * n;
     T gx, gy;
-    explicit_point_vjp<SCHEME>(ux + base, uy + base, lx + base, ly + base, i, j, n, s, gx, gy);
+    if constexpr (kEnsemble<S>)   // the cotangent of sample blockIdx.z is pulled back through member blockIdx.z's Jacobian
+        explicit_point_vjp<SCHEME>(ux + base, uy + base, lx + base, ly + base, i, j, n, member_const(s.plan, s.rows, blockIdx.z), gx, gy);
+    else
+        explicit_point_vjp<SCHEME>(ux + base, uy + base, lx + base, ly + base, i, j, n, s, gx, gy);
     const size_t p = base + (size_t)i * n + j;
     if (accumulate) {
         gx = ox[p] + gx;
@@ -753,6 +820,8 @@ struct tcfd_fvm_plan {
     size_t fft_ws;             // tcfd_ns2d_workspace_bytes of the transform plan, per batch, computed at call time
     int scheme;                // TCFD_FVM_*: the instantiation of k_fvm_stage / k_fvm_stage_vjp, read at every launch
     int tangent;               // 1: every call carries pairs, fields [0, B) the state and [B, 2 B) its perturbation
+    void* ens;                 // per-sample physics (tcfd_fvm_plan_set_ensemble): ens_count x {nu / density, -drag, forcing scale}
+    long ens_count;            //   in the field precision, or NULL / 0: a scalar plan, whose launches are what they always were
 };
 
 namespace {
@@ -775,10 +844,25 @@ StageConst<T> stage_const(const tcfd_fvm_plan* p, double dt) {
     return s;
 }
 
+// an ensemble plan steps exactly its own members, one field each (a tangent plan: the state and the perturbation of each).  Every
+// entry point that evaluates the explicit terms checks it before it touches the device, and the two stage launchers check it
+// again: row blockIdx.z of the table exists for every block they launch.
+int check_ensemble_batch(const tcfd_fvm_plan* p, long batch, const char* what) {
+    if (p->ens_count <= 0) return 0;
+    if (p->tangent && batch != 2 * p->ens_count)
+        return FAIL(TCFD_EINVAL, "%s: batch %ld on a tangent plan with per-sample parameters for %ld members, which takes 2 x %ld "
+                                 "fields (tcfd_fvm_plan_set_ensemble)", what, batch, p->ens_count, p->ens_count);
+    if (!p->tangent && batch != p->ens_count)
+        return FAIL(TCFD_EINVAL, "%s: batch %ld on a plan with per-sample parameters for %ld fields (tcfd_fvm_plan_set_ensemble)",
+                    what, batch, p->ens_count);
+    return 0;
+}
+
 template <typename T>
 int stage_launch(const tcfd_fvm_plan* p, const void* ux, const void* uy, const void* u0x, const void* u0y, void* kx, void* ky,
                  void* const* tx, void* const* ty, const double* c, const int* mode, int count, long batch, double dt,
                  hipStream_t st) {
+    if (int rc = check_ensemble_batch(p, batch, "fvm stage")) return rc;
     Targets<T> tg;
     tg.count = count;
     for (int t = 0; t < MAXT; ++t) {
@@ -790,13 +874,23 @@ int stage_launch(const tcfd_fvm_plan* p, const void* ux, const void* uy, const v
     // a tangent plan: the pair kernel over the B = batch / 2 samples, the perturbation B planes after the state
     const long half_batch = batch / 2;
     const size_t pair = (size_t)half_batch * p->n * p->n;
+    // an ensemble plan: the EnsConst instantiations on the member table.  No call splits its batch, so sample 0 of a launch is member 0.
+    const T* ens = (const T*)p->ens;
 #define STAGE(SCHEME)                                                                                                      \
-    if (p->tangent)                                                                                                        \
-        hipLaunchKernelGGL((k_fvm_stage_jvp<SCHEME, T>), cell_grid(p->n, half_batch), kCellBlock, 0, st, (const T*)ux,     \
+    if (ens && p->tangent)                                                                                                 \
+        hipLaunchKernelGGL((k_fvm_stage_jvp<SCHEME, T, EnsConst<T>>), cell_grid(p->n, half_batch), kCellBlock, 0, st,      \
+                           (const T*)ux, (const T*)uy, (const T*)u0x, (const T*)u0y, (const T*)p->fx, (const T*)p->fy,     \
+                           (T*)kx, (T*)ky, tg, EnsConst<T>{stage_const<T>(p, dt), ens}, p->n, pair);                       \
+    else if (ens)                                                                                                          \
+        hipLaunchKernelGGL((k_fvm_stage<SCHEME, T, EnsConst<T>>), cell_grid(p->n, batch), kCellBlock, 0, st, (const T*)ux, \
+                           (const T*)uy, (const T*)u0x, (const T*)u0y, (const T*)p->fx, (const T*)p->fy, (T*)kx, (T*)ky,   \
+                           tg, EnsConst<T>{stage_const<T>(p, dt), ens}, p->n);                                             \
+    else if (p->tangent)                                                                                                   \
+        hipLaunchKernelGGL((k_fvm_stage_jvp<SCHEME, T, StageConst<T>>), cell_grid(p->n, half_batch), kCellBlock, 0, st, (const T*)ux, \
                            (const T*)uy, (const T*)u0x, (const T*)u0y, (const T*)p->fx, (const T*)p->fy, (T*)kx, (T*)ky,   \
                            tg, stage_const<T>(p, dt), p->n, pair);                                                         \
     else                                                                                                                   \
-        hipLaunchKernelGGL((k_fvm_stage<SCHEME, T>), cell_grid(p->n, batch), kCellBlock, 0, st, (const T*)ux,              \
+        hipLaunchKernelGGL((k_fvm_stage<SCHEME, T, StageConst<T>>), cell_grid(p->n, batch), kCellBlock, 0, st, (const T*)ux, \
                            (const T*)uy, (const T*)u0x, (const T*)u0y, (const T*)p->fx, (const T*)p->fy, (T*)kx, (T*)ky,   \
                            tg, stage_const<T>(p, dt), p->n)
     switch (p->scheme) {
@@ -841,9 +935,16 @@ int apply_launch(const tcfd_fvm_plan* p, const void* px, const void* py, const v
 template <typename T>
 int stage_vjp_launch(const tcfd_fvm_plan* p, const void* ux, const void* uy, const void* lx, const void* ly, void* ox, void* oy,
                      int accumulate, long batch, double dt, hipStream_t st) {
+    if (int rc = check_ensemble_batch(p, batch, "fvm stage vjp")) return rc;
+    const T* ens = (const T*)p->ens;
 #define STAGE_VJP(SCHEME)                                                                                                  \
-    hipLaunchKernelGGL((k_fvm_stage_vjp<SCHEME, T>), cell_grid(p->n, batch), kCellBlock, 0, st, (const T*)ux,              \
-                       (const T*)uy, (const T*)lx, (const T*)ly, (T*)ox, (T*)oy, accumulate, stage_const<T>(p, dt), p->n)
+    if (ens)                                                                                                               \
+        hipLaunchKernelGGL((k_fvm_stage_vjp<SCHEME, T, EnsConst<T>>), cell_grid(p->n, batch), kCellBlock, 0, st,           \
+                           (const T*)ux, (const T*)uy, (const T*)lx, (const T*)ly, (T*)ox, (T*)oy, accumulate,             \
+                           EnsConst<T>{stage_const<T>(p, dt), ens}, p->n);                                                 \
+    else                                                                                                                   \
+        hipLaunchKernelGGL((k_fvm_stage_vjp<SCHEME, T, StageConst<T>>), cell_grid(p->n, batch), kCellBlock, 0, st, (const T*)ux, \
+                           (const T*)uy, (const T*)lx, (const T*)ly, (T*)ox, (T*)oy, accumulate, stage_const<T>(p, dt), p->n)
     switch (p->scheme) {
         case VAN_LEER: STAGE_VJP(VAN_LEER); break;
         case UPWIND: STAGE_VJP(UPWIND); break;
@@ -1024,6 +1125,7 @@ void tcfd_fvm_plan_destroy(tcfd_fvm_plan* p) {
     if (p->inv) (void)hipFree(p->inv);
     if (p->fx) (void)hipFree(p->fx);
     if (p->fy) (void)hipFree(p->fy);
+    if (p->ens) (void)hipFree(p->ens);
     if (p->fft) tcfd_ns2d_plan_destroy(p->fft);
     delete p;
 }
@@ -1044,6 +1146,40 @@ int tcfd_fvm_plan_set_tangent(tcfd_fvm_plan* p, int on) {
     return 0;
 }
 
+int tcfd_fvm_plan_set_ensemble(tcfd_fvm_plan* p, long count, const double* nu_over_density, const double* drag,
+                               const double* forcing_scale) {
+    if (!p) return FAIL(TCFD_EINVAL, "fvm_plan_set_ensemble: null plan");
+    if (count < 0) return FAIL(TCFD_EINVAL, "fvm_plan_set_ensemble: count %ld < 0", count);
+    if (count > 0 && !nu_over_density) return FAIL(TCFD_EINVAL, "fvm_plan_set_ensemble: nu_over_density is required when count > 0");
+    if (count > 0 && forcing_scale && !p->fx)
+        return FAIL(TCFD_EINVAL, "fvm_plan_set_ensemble: forcing scales on a plan without forcing tables (nothing to scale)");
+    void* table = nullptr;
+    if (count > 0) {
+        // the rows in the field precision, each value converted as stage_const converts the plan's scalars
+        const bool f64 = is_f64(p);
+        const size_t values = (size_t)count * ENS_ROW, bytes = values * real_bytes(p);
+        std::vector<double> rows(values);
+        for (long b = 0; b < count; ++b) {
+            rows[ENS_ROW * b + 0] = nu_over_density[b];
+            rows[ENS_ROW * b + 1] = -(drag ? drag[b] : p->drag);
+            rows[ENS_ROW * b + 2] = forcing_scale ? forcing_scale[b] : 1.0;
+        }
+        std::vector<float> rows32;
+        if (!f64) rows32.assign(rows.begin(), rows.end());
+        if (hipMalloc(&table, bytes) != hipSuccess) return FAIL(TCFD_ENOMEM, "fvm_plan_set_ensemble: hipMalloc(%zu)", bytes);
+        const hipError_t e = hipMemcpy(table, f64 ? (const void*)rows.data() : (const void*)rows32.data(), bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {   // set whole or not at all: the plan keeps the table it had
+            (void)hipFree(table);
+            return FAIL(TCFD_EHIP, "fvm_plan_set_ensemble: upload: %s", hipGetErrorString(e));
+        }
+    }
+    // (hipFree waits for the device: no launch of an earlier call still reads the old table)
+    if (p->ens) (void)hipFree(p->ens);
+    p->ens = table;
+    p->ens_count = count;
+    return 0;
+}
+
 size_t tcfd_fvm_workspace_bytes(const tcfd_fvm_plan* p, long batch) {
     if (!p || batch <= 0) return 0;
     return carve(p, batch, nullptr, kStep).total;
@@ -1054,6 +1190,7 @@ int tcfd_fvm_explicit_terms(const tcfd_fvm_plan* p, const void* ux, const void* 
     if (!p || !ux || !uy || !kx || !ky || batch <= 0) return FAIL(TCFD_EINVAL, "fvm_explicit_terms: bad argument");
     if (p->tangent && batch % 2)
         return FAIL(TCFD_EINVAL, "fvm_explicit_terms: batch %ld on a tangent plan, which takes pairs (batch = 2 B)", batch);
+    if (int rce = check_ensemble_batch(p, batch, "fvm_explicit_terms")) return rce;
     return stage_launch(p, ux, uy, ux, uy, kx, ky, nullptr, nullptr, nullptr, nullptr, 0, batch, dt, (hipStream_t)stream);
 }
 
@@ -1075,6 +1212,7 @@ int tcfd_fvm_step(const tcfd_fvm_plan* p, const void* ux_in, const void* uy_in, 
         return FAIL(TCFD_EINVAL, "fvm_step: bad argument");
     if (p->tangent && batch % 2)
         return FAIL(TCFD_EINVAL, "fvm_step: batch %ld on a tangent plan, which takes pairs (batch = 2 B)", batch);
+    if (int rce = check_ensemble_batch(p, batch, "fvm_step")) return rce;
     if (nstages < 1 || nstages > MAXT) return FAIL(TCFD_EINVAL, "fvm_step: %d stages (1 .. %d supported)", nstages, MAXT);
     for (int i = 0; i < nstages; ++i)
         for (int j = i; j < nstages; ++j)
@@ -1141,6 +1279,7 @@ int tcfd_fvm_explicit_terms_vjp(const tcfd_fvm_plan* p, const void* ux, const vo
     if (!p || !ux || !uy || !gx || !gy || !out_x || !out_y || batch <= 0)
         return FAIL(TCFD_EINVAL, "fvm_explicit_terms_vjp: bad argument");
     if (p->tangent) return FAIL(TCFD_EINVAL, "fvm_explicit_terms_vjp: a tangent plan (forward over reverse is not provided)");
+    if (int rce = check_ensemble_batch(p, batch, "fvm_explicit_terms_vjp")) return rce;
     if (out_x == gx || out_x == gy || out_y == gx || out_y == gy || out_x == ux || out_x == uy || out_y == ux || out_y == uy)
         return FAIL(TCFD_EINVAL, "fvm_explicit_terms_vjp: the output may not alias an input (the stencil reads neighbours)");
     return stage_vjp_launch(p, ux, uy, gx, gy, out_x, out_y, 0, batch, dt, (hipStream_t)stream);
@@ -1157,6 +1296,7 @@ int tcfd_fvm_step_vjp(const tcfd_fvm_plan* p, const void* saved, const void* gx,
     if (!p || !gx || !gy || !out_x || !out_y || batch <= 0 || steps < 0 || (steps > 0 && !saved) || !b || (nstages > 1 && !a))
         return FAIL(TCFD_EINVAL, "fvm_step_vjp: bad argument");
     if (p->tangent) return FAIL(TCFD_EINVAL, "fvm_step_vjp: a tangent plan (forward over reverse is not provided)");
+    if (int rce = check_ensemble_batch(p, batch, "fvm_step_vjp")) return rce;
     if (nstages < 1 || nstages > MAXT) return FAIL(TCFD_EINVAL, "fvm_step_vjp: %d stages (1 .. %d supported)", nstages, MAXT);
     for (int i = 0; i < nstages; ++i)
         for (int j = i; j < nstages; ++j)

@@ -24,6 +24,13 @@ state through the tangent instantiation of the stage kernel (``k_fvm_stage_jvp``
 ``torch.autograd.forward_ad`` given to ``forward`` / ``advance``, ``RKStepper.forward``, ``explicit_terms``, ``convect``,
 ``pressure_projection`` / ``PressureProjection.forward`` or ``get_trajectory_fvm`` runs the same calls; a component without a
 tangent counts as a zero tangent.  Forward over reverse is not provided.
+
+Ensembles: ``viscosity`` / ``drag`` / ``forcing_scale`` given per sample (a length-B sequence or a ``(B, 1, 1)`` tensor) make the
+equation an ENSEMBLE of B members.  Component ``b`` of a ``(B, n, n)`` state then runs with member ``b``'s values in every call
+above that evaluates the explicit terms -- stepping, ``explicit_terms``, the tangent-linear calls and dual numbers, and reverse
+mode with respect to the velocity -- on the per-sample instantiations of the same three stage kernels
+(``tcfd_fvm_plan_set_ensemble``): one plan and one launch per stage for the whole sweep.  The parameters are data: one that
+requires grad raises ``NotImplementedError``.  ``convect`` and the projection read no physics and are as they were.
 """
 from __future__ import annotations
 
@@ -40,6 +47,7 @@ import torch.nn as nn
 from . import _lib
 from . import fvm_autograd as _ad
 from . import interpolation
+from .equations import _ensemble_members
 from .grids import Grid
 
 _FP = {torch.float64: _lib.TCFD_C128, torch.float32: _lib.TCFD_C64}
@@ -260,7 +268,7 @@ class _FvmPlan:
 
     def __init__(self, n: int, dtype: torch.dtype, device: torch.device, h: float, nu: float, drag: float,
                  inverse: torch.Tensor, force: Optional[Tuple[torch.Tensor, torch.Tensor]],
-                 scheme: int = _lib.TCFD_FVM_VAN_LEER, tangent: bool = False):
+                 scheme: int = _lib.TCFD_FVM_VAN_LEER, tangent: bool = False, members=None):
         self.lib = _lib.load()
         self.n, self.dtype, self.device = n, dtype, torch.device(device)
         if self.device.type != "cuda":
@@ -286,6 +294,26 @@ class _FvmPlan:
         self.tangent = bool(tangent)   # a tangent plan steps pairs [u; du]: its calls go through the *_pair methods below
         if self.tangent:
             _lib.check(self.lib.tcfd_fvm_plan_set_tangent(handle, 1), "tcfd_fvm_plan_set_tangent")
+        self.members = 0   # B of an ensemble plan: every call but project then takes B fields (a tangent plan: 2 B)
+        if members is not None:
+            self.set_ensemble(*members)
+
+    def set_ensemble(self, nu_over_density=None, drag=None, forcing_scale=None) -> None:
+        """Per-sample physics (``tcfd_fvm_plan_set_ensemble``): field b of every later call runs with ``nu_over_density[b]``,
+        ``drag[b]`` (None: the plan's scalar drag) and ``forcing_scale[b]`` times the plan's forcing (None: 1).  Sequences of one
+        length B; no ``nu_over_density`` clears the table and the plan is scalar again."""
+        if not hasattr(self.lib, "tcfd_fvm_plan_set_ensemble"):   # added without a new ABI number: a stale library loads, but lacks it
+            raise _lib.TcfdError(f"{_lib.LIB_PATH} was built before per-sample parameters (tcfd_fvm_plan_set_ensemble) were "
+                                 "added: rebuild it with torch_cfd_amd._lib.build_library(force=True)")
+        count = 0 if nu_over_density is None else len(nu_over_density)
+        for name, v in (("drag", drag), ("forcing_scale", forcing_scale)):
+            if count and v is not None and len(v) != count:
+                raise ValueError(f"set_ensemble: {count} viscosities, {len(v)} values of {name}")
+        arr = lambda v: _lib.darray(v) if count and v is not None else None
+        with torch.cuda.device(self.device):
+            rc = self.lib.tcfd_fvm_plan_set_ensemble(self.handle, count, arr(nu_over_density), arr(drag), arr(forcing_scale))
+        _lib.check(rc, "tcfd_fvm_plan_set_ensemble")
+        self.members = count
 
     def workspace(self, batch: int, need: Optional[int] = None) -> torch.Tensor:
         """At least ``need`` bytes (default: what ``tcfd_fvm_step`` needs for ``batch``)."""
@@ -507,16 +535,28 @@ class NavierStokes2DFVMProjection(nn.Module):
     are differentiable with respect to ``u`` (``fvm_autograd.py``); under grad, ``forward`` runs one device call per step
     and keeps each step's input, ``steps * 2 * B * n^2 * w`` bytes, for its backward."""
 
-    def __init__(self, viscosity: float, grid: Grid, bcs=None, drag: float = 0.0, density: float = 1.0, forcing=None,
-                 solver: Optional[RKStepper] = None, convect: Optional[Convect] = _VAN_LEER_CONVECT, **kwargs):
+    def __init__(self, viscosity, grid: Grid, bcs=None, drag=0.0, density: float = 1.0, forcing=None,
+                 solver: Optional[RKStepper] = None, convect: Optional[Convect] = _VAN_LEER_CONVECT, forcing_scale=None,
+                 **kwargs):
+        """``viscosity`` / ``drag``: a float -- one physics for every field, as the reference -- or per-sample values: a 1-D
+        sequence / tensor of length B or a ``(B, 1, 1)`` tensor.  ``forcing_scale``: a float or a length-B sequence; sample b is
+        forced by ``forcing_scale[b] * forcing``.  Any per-sample argument makes the equation an ENSEMBLE of B members (single
+        values are repeated): component b of a ``(B, n, n)`` state runs with member b's values.  ``density`` is one value."""
         super().__init__()
         _check_periodic(bcs)
         _square_step(grid)
-        self.viscosity = viscosity
+        if forcing_scale is not None and forcing is None:
+            raise ValueError("forcing_scale without a forcing: there is nothing to scale")
+        members = _ensemble_members(viscosity, drag, forcing_scale)
+        self._ens_count = 0 if members is None else int(members[0].numel())
+        if members is None:   # the scalar equation: attributes and plan as they always were
+            self.viscosity, self.drag, self.forcing_scale = viscosity, drag, forcing_scale
+        else:                 # per-sample BUFFERS in the reference's broadcasting shape
+            for name, v in zip(("viscosity", "drag", "forcing_scale"), members):
+                self.register_buffer(name, v.reshape(-1, 1, 1))
         self.density = density
         self.grid = grid
         self.bcs = bcs
-        self.drag = drag
         self.forcing = forcing
         self.solver = solver
         self.advection = _as_convect(convect)
@@ -531,11 +571,41 @@ class NavierStokes2DFVMProjection(nn.Module):
         if self.forcing is None:
             return None
         f = self.forcing(self.grid, None)
-        return tuple(_tensor_of(c).detach().to("cpu", torch.float64) / self.density for c in f)
+        tables = tuple(_tensor_of(c).detach().to("cpu", torch.float64) / self.density for c in f)
+        if not self._ens_count and self.forcing_scale is not None:   # one amplitude for every field
+            tables = tuple(float(self.forcing_scale) * t for t in tables)
+        return tables
+
+    # -- per-sample parameters
+    def _member_tables(self):
+        return (self.viscosity, self.drag, self.forcing_scale)
+
+    def _members(self):
+        """None for the scalar equation, else ``(nu / density, drag, forcing_scale)`` of the B members as lists (no forcing
+        scales without a forcing: the plan has nothing to scale)."""
+        if not self._ens_count:
+            return None
+        nu, drag, fs = (t.detach().reshape(-1).to("cpu", torch.float64) for t in self._member_tables())
+        return (nu / self.density).tolist(), drag.tolist(), (fs.tolist() if self.forcing is not None else None)
+
+    def _check_members(self, ux: torch.Tensor, what: str) -> None:
+        """An ensemble steps exactly its B members, one ``(n, n)`` field each."""
+        if self._ens_count and (ux.ndim != 3 or ux.shape[0] != self._ens_count):
+            raise ValueError(f"{what}: an ensemble of B = {self._ens_count} members (viscosity / drag / forcing_scale given per "
+                             f"sample) takes (B, n, n) velocity components with B = {self._ens_count}, got {tuple(ux.shape)}")
 
     def _plan_key(self, dtype, device) -> tuple:
         inv = self._projection.solver.inverse
         fkey = None if self.forcing is None else getattr(self.forcing, "fingerprint", lambda: id(self.forcing))()
+        if not self._ens_count and self.forcing_scale is not None:   # one amplitude for every field: part of the forcing table
+            fkey = (fkey, float(self.forcing_scale))
+        if self._ens_count:   # the member values: a changed buffer (another storage, an in-place write) builds a new plan
+            for t in self._member_tables():
+                if t.requires_grad:
+                    raise NotImplementedError("per-sample parameters are data: a viscosity / drag / forcing_scale that requires "
+                                              "grad is not implemented (gradients with respect to the parameters are out of scope)")
+            return (torch.device(device), dtype, self.grid.shape[0], float(self.density), fkey, id(inv), inv._version,
+                    self.advection.scheme) + tuple((t.data_ptr(), t._version) for t in self._member_tables())
         return (torch.device(device), dtype, self.grid.shape[0], float(self.viscosity), float(self.density), float(self.drag),
                 fkey, id(inv), inv._version, self.advection.scheme)
 
@@ -545,9 +615,11 @@ class NavierStokes2DFVMProjection(nn.Module):
         plan = plans.get(key)
         if plan is None:
             plans.clear()
-            plan = _FvmPlan(self.grid.shape[0], dtype, device, _square_step(self.grid), self.viscosity / self.density,
-                            self.drag, self._projection.solver.inverse, self._force_tables(), self.advection.scheme,
-                            tangent=tangent)
+            members = self._members()
+            nu, drag = (members[0][0], members[1][0]) if members else (self.viscosity / self.density, self.drag)
+            plan = _FvmPlan(self.grid.shape[0], dtype, device, _square_step(self.grid), nu, drag,
+                            self._projection.solver.inverse, self._force_tables(), self.advection.scheme, tangent=tangent,
+                            members=members)
             plans[key] = plan
         return plan
 
@@ -585,12 +657,14 @@ class NavierStokes2DFVMProjection(nn.Module):
         """``((kx, ky), (dkx, dky))``: the explicit terms ``F(u)`` and their directional derivative ``J_F(u) du`` along the
         pair ``du`` (shapes and dtype of ``u``), one fused launch.  The tangent carries no forcing."""
         (ux, uy), (dux, duy) = _jvp_pairs(u, du, self.grid.shape[0], "explicit_terms_jvp")
+        self._check_members(ux, "explicit_terms_jvp")
         return self._plan(ux.dtype, ux.device, tangent=True).explicit_terms_pair(ux, uy, dux, duy, dt)
 
     def _tangent_steps(self, u, du, dt: float, steps: int, solver: Optional[RKStepper]):
         if solver is None:
             raise ValueError("NavierStokes2DFVMProjection: no RKStepper (pass solver=RKStepper.from_method(...))")
         (ux, uy), (dux, duy) = _jvp_pairs(u, du, self.grid.shape[0], "tangent_step")
+        self._check_members(ux, "tangent_step")
         solver._check_no_grad()
         a, b = solver.weights(dt)
         return self._plan(ux.dtype, ux.device, tangent=True).step_pair(ux, uy, dux, duy, dt, a, b, steps)
@@ -606,6 +680,7 @@ class NavierStokes2DFVMProjection(nn.Module):
         duals = _unpack_duals(ux, uy)
         if duals is not None:
             return _make_duals(*self.explicit_terms_jvp(*duals, dt))
+        self._check_members(ux, "explicit_terms")
         plan = self._plan(ux.dtype, ux.device)
         if _ad.wants_grad(ux, uy):
             return _ad.ExplicitTermsFn.apply(plan, dt, ux, uy)
@@ -623,6 +698,7 @@ class NavierStokes2DFVMProjection(nn.Module):
         if duals is not None:   # forward-mode dual numbers: the tangent-linear step carries them
             return _make_duals(*self._tangent_steps(*duals, dt, steps, solver))
         solver._check_no_grad()
+        self._check_members(ux, "advance")
         a, b = solver.weights(dt)
         plan = self._plan(ux.dtype, ux.device)
         if _ad.wants_grad(ux, uy):

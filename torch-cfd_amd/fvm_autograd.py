@@ -14,7 +14,8 @@ and its reverse, given the cotangent ``ubar`` of ``u_new`` (``P`` is symmetric, 
 ``StepFn`` keeps the input of every step and recomputes the stage states in the backward: a rollout of K steps holds
 ``K * 2 * B * n^2 * w`` bytes (``w`` = 8 for fp64, 4 for fp32) until its backward has run, plus the plan's workspace
 (``tcfd_fvm_step_vjp_workspace_bytes``: 16 fields and the transform scratch).  The backward passes are first order only: they
-are marked ``once_differentiable``, so a double backward raises instead of dropping second-order terms.  Gradients with
+are marked ``once_differentiable``, so a double backward raises instead of dropping second-order terms (on an ensemble plan,
+``tcfd_fvm_plan_set_ensemble``, already the recorded backward raises ``NotImplementedError``).  Gradients with
 respect to the tableau coefficients are not provided (``RKStepper`` raises for a tableau that requires grad).
 """
 from __future__ import annotations
@@ -46,6 +47,14 @@ def _like(shape, t: torch.Tensor) -> torch.Tensor:
     return torch.empty((), dtype=t.dtype, device=t.device).expand(shape)
 
 
+def _refuse_ensemble_double_backward(plan) -> None:
+    """A backward that is itself recorded (``create_graph=True``) on an ensemble plan: the adjoint kernels are first order, and
+    nothing composed stands behind them for per-sample physics."""
+    if torch.is_grad_enabled() and getattr(plan, "members", 0):
+        raise NotImplementedError("double backward (create_graph=True) through an ensemble with per-sample viscosity / drag / "
+                                  "forcing_scale is not implemented: the adjoint kernels are first order")
+
+
 class ExplicitTermsFn(torch.autograd.Function):
     """``(kx, ky) = explicit_terms(ux, uy)``; backward: ``J^T (kx_bar, ky_bar)`` by the gather kernel."""
 
@@ -57,8 +66,13 @@ class ExplicitTermsFn(torch.autograd.Function):
         return plan.explicit_terms(ux, uy, dt)
 
     @staticmethod
-    @once_differentiable
     def backward(ctx, gx, gy):
+        _refuse_ensemble_double_backward(ctx.plan)
+        return ExplicitTermsFn._backward(ctx, gx, gy)
+
+    @staticmethod
+    @once_differentiable
+    def _backward(ctx, gx, gy):
         ux, uy = ctx.saved_tensors
         gx, gy = cotangent_pair(gx, gy, ux)
         bx, by = ctx.plan.explicit_terms_vjp(ux, uy, gx, gy, ctx.dt)
@@ -95,8 +109,13 @@ class StepFn(torch.autograd.Function):
         return ox, oy
 
     @staticmethod
-    @once_differentiable
     def backward(ctx, gx, gy):
+        _refuse_ensemble_double_backward(ctx.plan)
+        return StepFn._backward(ctx, gx, gy)
+
+    @staticmethod
+    @once_differentiable
+    def _backward(ctx, gx, gy):
         (saved,) = ctx.saved_tensors
         gx, gy = cotangent_pair(gx, gy, _like(saved.shape[2:], saved))
         bx, by = ctx.plan.step_vjp(saved, gx, gy, ctx.dt, ctx.a, ctx.b)
