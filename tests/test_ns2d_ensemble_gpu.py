@@ -51,12 +51,19 @@ def scaled_err(a, b, scale_of):
     return (torch.linalg.norm((a - b).reshape(-1)) / torch.linalg.norm(s.reshape(-1))).item()
 
 
+def wave_number(n):
+    """4, the wave number of the goldens, wherever the grid resolves it; 2 at n = 8, where 4 is the Nyquist mode: sin(4 y) samples
+    to round-off in every bin there, which a forcing scale of 0 turns into exact zeros -- another plan (pruned, sparse forcing)
+    than the members with a non-zero scale get, and nothing of a forcing to compare."""
+    return 4 if n >= 16 else 2
+
+
 def ensemble_op(n, tag, dev, nu=NU, drag=DRAG, fscale=FSCALE, solver=None):
     import torch_cfd_amd as tc
 
     torch.set_default_dtype(REAL[tag])
     grid = tc.Grid(shape=(n, n), domain=((0, L), (0, L)))
-    forcing = tc.KolmogorovForcing(grid=grid, scale=1.0, wave_number=4, swap_xy=False)
+    forcing = tc.KolmogorovForcing(grid=grid, scale=1.0, wave_number=wave_number(n), swap_xy=False)
     return tc.NavierStokes2DSpectral(list(nu), grid, drag=list(drag), smooth=True, forcing_fn=forcing, forcing_scale=list(fscale),
                                      solver=solver or tc.RK4CrankNicolsonStepper()).to(dev)
 
@@ -66,7 +73,7 @@ def scalar_op(n, tag, dev, nu, drag, fscale, solver=None):
 
     torch.set_default_dtype(REAL[tag])
     grid = tc.Grid(shape=(n, n), domain=((0, L), (0, L)))
-    forcing = tc.KolmogorovForcing(grid=grid, scale=fscale, wave_number=4, swap_xy=False)
+    forcing = tc.KolmogorovForcing(grid=grid, scale=fscale, wave_number=wave_number(n), swap_xy=False)
     return tc.NavierStokes2DSpectral(nu, grid, drag=drag, smooth=True, forcing_fn=forcing,
                                      solver=solver or tc.RK4CrankNicolsonStepper()).to(dev)
 
@@ -154,13 +161,23 @@ def _compare_with_scalar_ops(n, tag, dev, fscale, bit_equal):
     return info
 
 
-@pytest.mark.parametrize("n", [64, 96, 80, 512, 1024])
+@pytest.mark.parametrize("n", [8, 16, 32, 64, 128, 256, 512, 1024, 2048, 96, 192, 384, 768, 1536, 80, 160, 320, 640, 1280])
 @pytest.mark.parametrize("tag", ["f64", "f32"])
 @pytest.mark.parametrize("scales", ["ones", "scaled"])
 def test_member_equals_scalar_operator(n, tag, scales, dev):
-    """Member b of one ensemble call against a scalar operator (nu_b, drag_b) of the same build on a batch of one, 3 steps.  With
-    forcing scales of 1 both sides evaluate the same roundings: the same bits."""
-    _compare_with_scalar_ops(n, tag, dev, ONES if scales == "ones" else FSCALE, bit_equal=scales == "ones")
+    """Member b of one ensemble call against a scalar operator (nu_b, drag_b) of the same build on a batch of one, 3 steps, on a
+    white state (``random_state``), at every fused size up to 2048: the scalar kernels of each size are held to the CPU oracle on
+    full-band spectra by tests/test_ns2d_white_spectrum_gpu.py.  With forcing scales of 1 both sides evaluate the same roundings:
+    the same bits.
+
+    n = 8 steps its member of forcing scale 0 with scale 0.25 instead: a plan keeps its forcing as a sparse list while
+    ``64 nnz <= n m``, which on the 40 bins of that grid only the empty list of a zero forcing meets, so the scalar twin of a
+    zero-scale member runs the sparse form next to the ensemble's dense table and "the same kernels on both sides" cannot hold.
+    Every other size keeps the zero member."""
+    fscale = ONES if scales == "ones" else FSCALE
+    if n == 8:
+        fscale = tuple(f or 0.25 for f in fscale)
+    _compare_with_scalar_ops(n, tag, dev, fscale, bit_equal=scales == "ones")
 
 
 @pytest.mark.parametrize("var,value,n", [("TCFD_FORCE_TABLES", "1", 128), ("TCFD_NO_PRUNE", "1", 128), ("TCFD_NYQ_PACK", "0", 128),
