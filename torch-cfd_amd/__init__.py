@@ -28,6 +28,7 @@ from .fvm import advection  # noqa: F401
 from .spectral import (  # noqa: F401
     brick_wall_filter_2d,
     fft_mesh_2d,
+    orthonormalize_tangents,
     spectral_curl_2d,
     spectral_div_2d,
     spectral_grad_2d,

@@ -15,6 +15,7 @@
 
 #include "tcfd_ns2d_plan.hpp"
 #include "../../include/tcfd_ns2d_adjoint.h"
+#include "../../include/tcfd_ns2d_bundle.h"
 
 using namespace tcfd;
 
@@ -250,6 +251,7 @@ extern "C" int tcfd_ns2d_plan_create(tcfd_ns2d_plan** out, int n, int dtype, con
     p->tune.nt_planes = env_int("TCFD_NT_PLANES", -1);
     p->tune.rows_v = env_int("TCFD_ROWS_V", 0);
     p->tune.chunk = env_int("TCFD_CHUNK", -1);
+    p->tune.bundle_rows = env_int("TCFD_BUNDLE_ROWS", -1);
     p->tune.cols_xl = env_int("TCFD_COLS_XL", 1);
     p->tune.nyq_pack = env_int("TCFD_NYQ_PACK", 1);
     p->tune.graph = env_int("TCFD_GRAPH", -1);
@@ -388,13 +390,17 @@ extern "C" int tcfd_ns2d_plan_info(const tcfd_ns2d_plan* p, int* separable, int*
 // that its working set -- 4 planes + advection + RK accumulator + padded state, 7 workspace fields per batch element --
 // fits the 256 MB Infinity Cache (measured on MI355X, steps/s per call: 1024^2 x 64 fp64 122.7 -> 129.3 at 4 fields
 // per chunk, 114.5 at 5; 512^2 x 64 fp64 408 -> 501 at 16).  Chunks are balanced.
+// the seven-field working sets (4 planes + advection + RK accumulator + padded state of one field) that fit the cache
+static long cache_fields(const tcfd_ns2d_plan* p) {
+    const size_t per_field = 7 * (size_t)p->n * p->ldw * (p->dtype == TCFD_C128 ? 16 : 8);
+    // 61/64 of the cache (244 of 256 MB, the measured optimum on MI355X: 4 fields of 1024^2 fp64 = 239 MB fit, 5 do not)
+    return (long)((p->tune.cache_bytes / 64 * 61) / per_field);
+}
 static long chunk_fields(const tcfd_ns2d_plan* p, long batch) {
     long c = p->tune.chunk;
     if (c == 0) return batch;
     if (c < 0) {
-        const size_t per_field = 7 * (size_t)p->n * p->ldw * (p->dtype == TCFD_C128 ? 16 : 8);
-        // 61/64 of the cache (244 of 256 MB, the measured optimum on MI355X: 4 fields of 1024^2 fp64 = 239 MB fit, 5 do not)
-        c = (long)((p->tune.cache_bytes / 64 * 61) / per_field);
+        c = cache_fields(p);
         // fewer than 3 fields per chunk: only at 2048^2, where ONE field is a whole round of workgroups (258 column tiles) and
         // most of its working set (237 of 244 MB) still fits: 16 fields 12.8 -> 11.5 ms per step with single-field chunks; at
         // 1536^2 / 1280^2 (1 - 2 fields would fit, 194 / 162 workgroups per field) the whole batch at once is faster
@@ -569,6 +575,117 @@ extern "C" int tcfd_ns2d_step_jvp(const tcfd_ns2d_plan* p, const void* w_in, con
         const size_t o = (size_t)b0 * esz;
         rc = NS2D_SIZED(p, step_jvp, p, (const unsigned char*)w_in + o, (const unsigned char*)dw_in + o, (unsigned char*)w_out + o,
                         (unsigned char*)dw_out + o, nb, nstages, fa, beta, gdt, mu_num, mu_den, base0, steps, ws, st);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------ tangent bundle: one state, K tangents per call
+// Fields per chunk and tangents per group.  A chunk of c states is in flight with its own plane set and those of kg tangents:
+// (1 + kg) c of the 7-field working sets chunk_fields sizes the cache for (`cap` of them fit; TCFD_CHUNK > 0 sets cap, 0 turns
+// chunking off).
+//   cap >= K + 1 : every tangent in one group, c = cap / (K + 1) states per chunk (balanced) -- K = 1 is jvp_chunk_fields' rule
+//   2 <= cap < K + 1 : one state per chunk, kg = cap - 1 tangents per group (balanced): the state's planes stay on die while the
+//                  groups pass, its column pass runs once per stage and its row transforms once per group
+//   cap < 2      : nothing stays on die whatever the grouping (n >= 1280 in fp64, n >= 2048 in fp32): one state, one group
+// The scratch is bundle_fields(K, kg) chunk-sized fields.
+struct BundleShape { long chunk; int kg; };
+constexpr int BUNDLE_MAX_TANGENTS = 65535;
+// the largest chunk and group the rule allows (a call balances both below these)
+static BundleShape bundle_limits(const tcfd_ns2d_plan* p, long batch, int ntan) {
+    long cap = p->tune.chunk;
+    if (cap == 0) return {batch, ntan};
+    if (cap < 0) cap = cache_fields(p);      // chunk_fields' budget
+    if (cap >= (long)ntan + 1) return {std::min(batch, cap / (ntan + 1)), ntan};
+    if (cap >= 2) return {1, (int)(cap - 1)};
+    return {1, ntan};
+}
+static BundleShape bundle_shape(const tcfd_ns2d_plan* p, long batch, int ntan) {
+    const BundleShape lim = bundle_limits(p, batch, ntan);
+    auto balanced = [](long total, long per) {
+        const long parts = (total + per - 1) / per;
+        return (total + parts - 1) / parts;
+    };
+    return {balanced(batch, lim.chunk), (int)balanced(ntan, lim.kg)};
+}
+
+// What the rule's limits need, and never less than a call with fewer tangents needs: the chunk shrinks as K grows, so the product
+// fields x chunk is not monotone by itself -- a caller who sizes one buffer for its largest bundle can rely on it for every smaller one.
+extern "C" size_t tcfd_ns2d_bundle_workspace_bytes(const tcfd_ns2d_plan* p, long batch, int ntangents) {
+    if (!p || batch <= 0 || ntangents < 1 || ntangents > BUNDLE_MAX_TANGENTS) return 0;
+    size_t need = 0;
+    for (int k = 1; k <= ntangents; ++k) {
+        const BundleShape lim = bundle_limits(p, batch, k);
+        need = std::max(need, (size_t)bundle_fields(k, lim.kg) * field_bytes(p, lim.chunk));
+    }
+    return need;
+}
+
+static bool ranges_overlap(const void* a, size_t an, const void* b, size_t bn) {
+    const unsigned char *a0 = (const unsigned char*)a, *b0 = (const unsigned char*)b;
+    return a0 < b0 + bn && b0 < a0 + an;
+}
+// the checks the two bundle calls share after their null / count checks; the launches of one chunk hold (kg + 1) * chunk fields at most
+static int check_bundle(const tcfd_ns2d_plan* p, const char* what, long batch, int ntangents, void* ws, size_t ws_bytes) {
+    if (ntangents < 1 || ntangents > BUNDLE_MAX_TANGENTS)
+        return fail(TCFD_EINVAL, "%s: ntangents must be in [1, %d] (got %d)", what, BUNDLE_MAX_TANGENTS, ntangents);
+    if (int rce = refuse_ensemble(p, what)) return rce;
+    if (batch > max_batch(p) / ntangents)
+        return fail(TCFD_EINVAL, "%s: batch %ld x %d tangents exceeds the largest batch of one call at n = %d (%ld fields)", what,
+                    batch, ntangents, p->n, max_batch(p));
+    return check_ws(p, batch, ws, ws_bytes, tcfd_ns2d_bundle_workspace_bytes(p, batch, ntangents));
+}
+
+extern "C" int tcfd_ns2d_explicit_terms_jvp_bundle(const tcfd_ns2d_plan* p, const void* w, const void* dw, void* out_f,
+                                                   void* out_df, long batch, int ntangents, void* ws, size_t ws_bytes,
+                                                   void* stream) {
+    if (!p || !w || !dw || !out_df || batch <= 0) return fail(TCFD_EINVAL, "explicit_terms_jvp_bundle: bad argument");
+    if (int rc = check_bundle(p, "explicit_terms_jvp_bundle", batch, ntangents, ws, ws_bytes)) return rc;
+    const size_t esz = (p->dtype == TCFD_C128 ? 16 : 8) * (size_t)p->n * p->m;
+    const size_t sb = (size_t)batch * esz, tb = (size_t)ntangents * sb;
+    // the groups of a chunk and the chunks of a call run one after the other: an output that overlapped an input would be read back
+    if (ranges_overlap(out_df, tb, w, sb) || ranges_overlap(out_df, tb, dw, tb) ||
+        (out_f && (ranges_overlap(out_f, sb, w, sb) || ranges_overlap(out_f, sb, dw, tb) || ranges_overlap(out_f, sb, out_df, tb))))
+        return fail(TCFD_EINVAL, "explicit_terms_jvp_bundle: the outputs must not overlap the inputs or each other");
+    hipStream_t st = (hipStream_t)stream;
+    const BundleShape sh = bundle_shape(p, batch, ntangents);
+    const size_t ts = (size_t)batch * p->n * p->m;      // elements between two tangents
+    for (long b0 = 0; b0 < batch; b0 += sh.chunk) {
+        const long nb = std::min(sh.chunk, batch - b0);
+        const size_t o = (size_t)b0 * esz;
+        int rc = NS2D_SIZED(p, explicit_jvp_bundle, p, (const unsigned char*)w + o, (const unsigned char*)dw + o,
+                            out_f ? (unsigned char*)out_f + o : nullptr, (unsigned char*)out_df + o, ts, nb, ntangents, sh.kg, ws, st);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+extern "C" int tcfd_ns2d_step_jvp_bundle(const tcfd_ns2d_plan* p, const void* w_in, const void* dw_in, void* w_out, void* dw_out,
+                                         long batch, int ntangents, int nstages, const double* fa, const double* beta,
+                                         const double* gdt, const double* mu_num, const double* mu_den, const int* base0,
+                                         int steps, void* ws, size_t ws_bytes, void* stream) {
+    if (!p || !w_in || !dw_in || !w_out || !dw_out || !beta || !gdt || !mu_num)
+        return fail(TCFD_EINVAL, "step_jvp_bundle: null argument");
+    if (batch <= 0 || steps <= 0 || nstages <= 0) return fail(TCFD_EINVAL, "step_jvp_bundle: batch/steps/nstages must be > 0");
+    if (int rc = check_bundle(p, "step_jvp_bundle", batch, ntangents, ws, ws_bytes)) return rc;
+    const size_t esz = (p->dtype == TCFD_C128 ? 16 : 8) * (size_t)p->n * p->m;
+    const size_t sb = (size_t)batch * esz, tb = (size_t)ntangents * sb;
+    // a state array and a tangent array never share memory; an output may BE its input (in place: every element is read before it
+    // is written, by the same thread), but not overlap it shifted -- a later chunk would read what an earlier one wrote
+    if (ranges_overlap(w_out, sb, dw_out, tb) || ranges_overlap(w_out, sb, dw_in, tb) || ranges_overlap(dw_out, tb, w_in, sb) ||
+        ranges_overlap(w_in, sb, dw_in, tb))
+        return fail(TCFD_EINVAL, "step_jvp_bundle: the state and the tangent arrays must not overlap");
+    if ((w_out != w_in && ranges_overlap(w_out, sb, w_in, sb)) || (dw_out != dw_in && ranges_overlap(dw_out, tb, dw_in, tb)))
+        return fail(TCFD_EINVAL, "step_jvp_bundle: an output overlaps its input without being it (identical or disjoint)");
+    hipStream_t st = (hipStream_t)stream;
+    const BundleShape sh = bundle_shape(p, batch, ntangents);
+    const size_t ts = (size_t)batch * p->n * p->m;
+    for (long b0 = 0; b0 < batch; b0 += sh.chunk) {
+        const long nb = std::min(sh.chunk, batch - b0);
+        const size_t o = (size_t)b0 * esz;
+        int rc = NS2D_SIZED(p, step_jvp_bundle, p, (const unsigned char*)w_in + o, (const unsigned char*)dw_in + o,
+                            (unsigned char*)w_out + o, (unsigned char*)dw_out + o, ts, nb, ntangents, sh.kg, nstages, fa, beta, gdt,
+                            mu_num, mu_den, base0, steps, ws, st);
         if (rc) return rc;
     }
     return 0;

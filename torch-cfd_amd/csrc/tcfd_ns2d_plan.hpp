@@ -73,6 +73,8 @@ struct Tuning {
     int cols_xl;             // TCFD_COLS_XL: cross-lane column transforms where available (1 = default)
     int nyq_pack;            // TCFD_NYQ_PACK: packed Nyquist column in the step (1 = default where the plan allows it)
     int chunk;               // TCFD_CHUNK: fields per chunk of a batched call (0 = whole batch at once, -1 = cache sized)
+    int bundle_rows;         // TCFD_BUNDLE_ROWS: row pass of the tangent-bundle calls: -1 = per size (bundle_two_pass), 0 = the two-pass
+                             // form of k_rows_jvp everywhere, 1 = k_rows_jvp_bundle wherever its stash fits a CU's LDS (A/B of the two)
     int graph;               // TCFD_GRAPH: hipGraph replay of interior steps (1 = on; off by default since round 4: plain stream
                              // launches measured 3-13 % faster than replay for every small problem, tests/micro/graph_crossover.py)
     int overlap;             // TCFD_OVERLAP: two half batches on two streams (opt-in experiment)
@@ -199,6 +201,54 @@ static JvpWs<T> carve_jvp(const tcfd_ns2d_plan* p, void* ws, long batch) {
     return w;
 }
 
+// Scratch of the tangent-BUNDLE calls (one state, K tangents; tcfd_ns2d_*_jvp_bundle): chunk-sized fields again.  The plane sets
+// and advection fields exist for the state and for ONE GROUP of kg <= K tangents (the tangents pass through the sweep group by
+// group: bundle_shape in tcfd_ns2d.hip); everything the stepper carries from stage to stage exists K times.  9 + 5 kg + 4 K fields.
+// The group's planes are stored [plane][tangent][field]: `dplane_stride` apart per plane, `plane_stride` apart per tangent, so
+// that ONE column launch over kg * batch fields fills or drains a group.  dF, dh and ds hold K tangents of batch fields each in
+// the caller's pitch, tangent after tangent (`tan_stride` elements apart).
+static inline int bundle_fields(int ntan, int kg) { return 9 + 5 * kg + 4 * ntan; }
+template <typename T>
+struct BundleWs {
+    cx<T>* planes;        // 4: the state's planes
+    cx<T>* dplanes;       // 4 kg
+    cx<T>* adv;           // 1
+    cx<T>* dadv;          // kg
+    cx<T>* F;             // 1: F(u) of the stage (caller layout, pitch m)
+    cx<T>* h;             // 1
+    cx<T>* s[2];          // 2: intermediate states
+    cx<T>* dF;            // K
+    cx<T>* dh;            // K
+    cx<T>* ds[2];         // K each
+    size_t plane_stride;  // elements of one chunk-sized field
+    size_t dplane_stride; // kg * plane_stride
+    size_t tan_stride;    // batch * n * m
+};
+template <typename T>
+static BundleWs<T> carve_bundle(const tcfd_ns2d_plan* p, void* ws, long batch, int ntan, int kg) {
+    const size_t fb = field_bytes(p, batch);
+    unsigned char* base = (unsigned char*)ws;
+    auto at = [&](long i) { return (cx<T>*)(base + (size_t)i * fb); };
+    BundleWs<T> w;
+    long i = 0;
+    w.planes = at(i); i += 4;
+    w.dplanes = at(i); i += 4L * kg;
+    w.adv = at(i); i += 1;
+    w.dadv = at(i); i += kg;
+    w.F = at(i); i += 1;
+    w.h = at(i); i += 1;
+    w.s[0] = at(i); i += 1;
+    w.s[1] = at(i); i += 1;
+    w.dF = at(i); i += ntan;
+    w.dh = at(i); i += ntan;
+    w.ds[0] = at(i); i += ntan;
+    w.ds[1] = at(i);
+    w.plane_stride = fb / sizeof(cx<T>);
+    w.dplane_stride = (size_t)kg * w.plane_stride;
+    w.tan_stride = (size_t)batch * p->n * p->m;
+    return w;
+}
+
 // Scratch of the adjoint model (tcfd_ns2d_step_vjp): the 8 fields of `Ws` for the forward and the adjoint sweeps of the explicit
 // terms (which touch `adv` and `planes` only), with the three fields those sweeps leave alone put to use, then 4 fields of X_f,
 // the cotangent of the step's initial state and the recomputed stage states u_1 .. u_{nstages-1}: 12 + nstages fields.
@@ -294,6 +344,15 @@ template <typename T>
 int step_jvp(const tcfd_ns2d_plan* p, const void* w_in, const void* dw_in, void* w_out, void* dw_out, long batch, int nstages,
              const double* fa, const double* beta, const double* gdt, const double* mu_num, const double* mu_den,
              const int* base0, int steps, void* ws, hipStream_t st);
+// one chunk of the tangent-bundle calls: ntan tangents per state, kg of them per pass through the sweep; tan_stride: elements
+// between two tangents of the caller's arrays (the whole call's batch * n * m)
+template <typename T>
+int explicit_jvp_bundle(const tcfd_ns2d_plan* p, const void* w, const void* dw, void* out_f, void* out_df, size_t tan_stride,
+                        long batch, int ntan, int kg, void* ws, hipStream_t st);
+template <typename T>
+int step_jvp_bundle(const tcfd_ns2d_plan* p, const void* w_in, const void* dw_in, void* w_out, void* dw_out, size_t tan_stride,
+                    long batch, int ntan, int kg, int nstages, const double* fa, const double* beta, const double* gdt,
+                    const double* mu_num, const double* mu_den, const int* base0, int steps, void* ws, hipStream_t st);
 // one chunk of tcfd_ns2d_step_vjp; saved_step_stride: elements between the saved inputs of two consecutive steps
 template <typename T>
 int step_vjp(const tcfd_ns2d_plan* p, const void* saved, size_t saved_step_stride, const void* g_out, const void* pre,

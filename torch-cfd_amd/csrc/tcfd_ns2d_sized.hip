@@ -974,6 +974,121 @@ __global__ __launch_bounds__((RowGeom<T, N, EPT, THR>::THREADS)) void k_rows_jvp
     }
 }
 
+// ---- row pass of a BUNDLE of tangents: one state, K perturbations -------------------------------------------------------------
+// k_rows_jvp carries one perturbation per state, so K perturbations of one trajectory transform the state's four planes K times.
+// Here a group transforms them ONCE per row pair, keeps the four physical-space rows and folds the K perturbations against them:
+//     p    = -(u dxw + v dyw)                                          -> adv            (skipped when adv is null)
+//     dp_k = -(ddxw_k u + dxw du_k + ddyw_k v + dyw dv_k)              -> dadv + k dtan_stride,      k < ntan
+// 4 + 4 K c2r and 1 + K r2c per row pair (K replicated k_rows_jvp sweeps: 8 K and 2 K).  The sums are accumulated in the order of
+// k_rows_jvp, term by term; the BITS are still not the single-tangent kernel's: hipcc contracts multiply-adds kernel by kernel, and
+// the two differ in the last place (measured: 2.5e-16 fp64, 1e-7 fp32 relative L2).  Member k does have the bits of the
+// K = 1 bundle call, whatever the other members hold.
+// THE STASH.  Every transform of a group leaves element j + t G of the row pair in register t of lane j, so the lane that needs
+// u, dxw, v, dyw at an element is the lane that produced them: the kept rows are lane-private and need no barrier.  They live in
+// LDS behind the groups' exchange buffers, 4 EPT elements per lane, stored [plane][t][thread of the workgroup]: consecutive lanes
+// touch consecutive 8 / 16-byte slots whatever the group size, so every stash access is conflict free (a per-group layout puts the
+// groups of one wave a multiple of the bank period apart).  Live registers: the working transform and ONE accumulator (p, then
+// dp_k) -- two arrays of EPT elements against the four of k_rows_jvp, which is why the 12-element fp64 sizes need no second pass.
+// LDS per lane is 5 EPT elements (exchange + stash): 640 B in fp64 at EPT = 8, so occupancy is set by LDS, not by registers
+// (BundleGeom, bundle_two_pass below).  Workgroups are ONE wave (or one group where a group is wider): the LDS per lane is fixed,
+// so smaller workgroups cost no occupancy and pack the CU's 160 KB in finer grains.
+// The state's four transforms and the 4 K tangent transforms are two loops that are NOT unrolled, for k_rows_jvp's reason.
+template <typename T, int N, int EPT>
+struct BundleGeom {
+    static constexpr int G = N / EPT;
+    static constexpr int THREADS = G >= 64 ? G : 64;
+    static constexpr int GROUPS = THREADS / G;
+    static constexpr int XCH_PER_GROUP = lds_elems<N, EPT, 1, true>();
+    static constexpr int STASH_ELEMS = 4 * EPT * THREADS;                 // == 4 N per group
+    static constexpr size_t LDS_BYTES = ((size_t)GROUPS * XCH_PER_GROUP + STASH_ELEMS) * sizeof(cx<T>);
+};
+
+template <typename T, int N, int EPT>
+__global__ __launch_bounds__((BundleGeom<T, N, EPT>::THREADS)) void k_rows_jvp_bundle(
+    const cx<T>* __restrict__ planes, size_t plane_stride, const cx<T>* __restrict__ dplanes, size_t dplane_stride,
+    size_t dtan_stride, cx<T>* __restrict__ adv, cx<T>* __restrict__ dadv, size_t dadv_stride, const cx<T>* __restrict__ tw,
+    long npairs, int ld, int ntan) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    using Gm = BundleGeom<T, N, EPT>;
+    constexpr int G = Gm::G;
+    constexpr bool WG = (G > 64);
+    constexpr int TH = Gm::THREADS;
+    const int grp = threadIdx.x / G;
+    const int j = threadIdx.x % G;
+    cx<T>* lds = reinterpret_cast<cx<T>*>(smem_raw) + (size_t)grp * Gm::XCH_PER_GROUP;
+    cx<T>* stash = reinterpret_cast<cx<T>*>(smem_raw) + (size_t)Gm::GROUPS * Gm::XCH_PER_GROUP + threadIdx.x;
+    const long stride = (long)gridDim.x * Gm::GROUPS;
+    long pair = (long)blockIdx.x * Gm::GROUPS + grp;
+    const long iters = (npairs + stride - 1) / stride;   // every group runs the same number of iterations (workgroup barriers)
+    // blockIdx.y: the segment of the tangents this workgroup folds (see the launcher); segment 0 also writes p
+    const int kper = (ntan + (int)gridDim.y - 1) / (int)gridDim.y;
+    const int k_lo = (int)blockIdx.y * kper, k_hi = min(ntan, k_lo + kper);
+    const bool do_p = adv && blockIdx.y == 0;   // block-uniform
+    for (long it = 0; it < iters; ++it, pair += stride) {
+        const bool valid = pair < npairs;
+        const long cur = valid ? pair : npairs - 1;
+        const size_t off = (size_t)cur * 2 * (size_t)ld;
+        cx<T> w[EPT], a[EPT];
+#pragma unroll
+        for (int t = 0; t < EPT; ++t) a[t] = mk<T>((T)0, (T)0);
+        // the state: stash slot s = 0 .. 3 holds u, dxw, v, dyw (planes 0, 2, 1, 3); p takes u dxw at s = 1 and v dyw at s = 3
+#pragma unroll 1
+        for (int s = 0; s < 4; ++s) {
+            const int f = (s & 1) ? 2 + (s >> 1) : (s >> 1);
+            const cx<T>* rowA = planes + (size_t)f * plane_stride + off;
+            {
+                RawPair<T, EPT> H;
+                load_raw<T, N, EPT>(H, rowA, rowA + ld, j);
+                pack_herm<T, N, EPT, WG>(w, H, lds, j);
+            }
+            tile_fft<T, N, EPT, +1, 1, true, WG>(w, lds, tw, j, 0);
+#pragma unroll
+            for (int t = 0; t < EPT; ++t) stash[(s * EPT + t) * TH] = w[t];
+            if ((s & 1) && do_p) {
+#pragma unroll
+                for (int t = 0; t < EPT; ++t) {
+                    const cx<T> k = stash[((s - 1) * EPT + t) * TH];
+                    a[t] = mk<T>(a[t].x + k.x * w[t].x, a[t].y + k.y * w[t].y);
+                }
+            }
+        }
+        if (do_p) {
+#pragma unroll
+            for (int t = 0; t < EPT; ++t) a[t] = mk<T>(-a[t].x, -a[t].y);
+            tile_fft<T, N, EPT, -1, 1, true, WG>(a, lds, tw, j, 0);
+            unpack_store_pair<T, N, EPT>(a, lds, adv + off, adv + off + ld, j, valid);
+        }
+        // the tangents: transform q = 0 .. 3 of tangent k is d(dxw), du, d(dyw), dv (planes 2, 0, 3, 1), folded against stash slot q
+#pragma unroll 1
+        for (int kt = k_lo; kt < k_hi; ++kt) {
+            const cx<T>* dset = dplanes + (size_t)kt * dtan_stride + off;
+#pragma unroll
+            for (int t = 0; t < EPT; ++t) a[t] = mk<T>((T)0, (T)0);
+#pragma unroll 1
+            for (int q = 0; q < 4; ++q) {
+                const int f = (q & 1) ? (q >> 1) : 2 + (q >> 1);
+                const cx<T>* rowA = dset + (size_t)f * dplane_stride;
+                {
+                    RawPair<T, EPT> H;
+                    load_raw<T, N, EPT>(H, rowA, rowA + ld, j);
+                    pack_herm<T, N, EPT, WG>(w, H, lds, j);
+                }
+                tile_fft<T, N, EPT, +1, 1, true, WG>(w, lds, tw, j, 0);
+#pragma unroll
+                for (int t = 0; t < EPT; ++t) {
+                    const cx<T> k = stash[(q * EPT + t) * TH];
+                    a[t] = mk<T>(a[t].x + w[t].x * k.x, a[t].y + w[t].y * k.y);
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < EPT; ++t) a[t] = mk<T>(-a[t].x, -a[t].y);
+            tile_fft<T, N, EPT, -1, 1, true, WG>(a, lds, tw, j, 0);
+            cx<T>* o = dadv + (size_t)kt * dadv_stride + off;
+            unpack_store_pair<T, N, EPT>(a, lds, o, o + ld, j, valid);
+        }
+    }
+}
+
 // ---- row pass, one plane per transform ("v5") --------------------------------------------------
 // Round 1 rode two PLANES of one row through a complex transform, so the transformed velocity rows of BOTH rows of a pair
 // stayed live while the gradient planes were transformed (256 VGPR + 84 AGPR, one wave per SIMD at 1024^2 fp64; kernels v3 / v4,
@@ -2144,6 +2259,218 @@ static int step_jvp_impl(const tcfd_ns2d_plan* p, const void* w_in, const void* 
     return 0;
 }
 
+// ------------------------------------------------------------------ tangent bundle: one state, K tangents
+// The sweep of explicit_jvp_impl with the state's share done once: MODE_A on w, then group by group (kg tangents, bundle_shape in
+// tcfd_ns2d.hip) MODE_A on the group's tangents, ONE row pass for the group (k_rows_jvp_bundle; the first group's also writes p),
+// MODE_F on p and on the group's dp.  A group's planes are [plane][tangent][field], so its column passes are single launches
+// over kg * batch fields wherever the tangents are tangent_stride == batch fields apart (always inside a step; at the call's
+// edges when the call is one chunk).
+
+// Sizes that run the two-pass row kernels instead (k_rows_jvp PART = 1 once, PART = 2 per tangent -- the state's planes are read
+// again per tangent, but nothing of the state is repeated in the column passes or the stage update): those whose stash leaves a
+// CU fewer than two workgroups.  A workgroup is one wave or one group, and holds 5 EPT elements of LDS per lane; above 80 KB one
+// workgroup -- one or two waves -- would own the CU's 160 KB alone and nothing would hide its transforms' exchange latency.
+// fp64: n = 5 * 2^k (20 elements per lane, 100 KB), 1536 (120 KB), 2048 (160 KB), 4096 (320 KB: not launchable); fp32: 4096 (160 KB).
+template <typename T, int N>
+static constexpr bool bundle_two_pass() {
+    return BundleGeom<T, N, Cfg<T, N>::ROW_EPT>::LDS_BYTES > 80 * 1024;
+}
+// TCFD_BUNDLE_ROWS = 0 runs the two-pass form at every size (the A/B that DESIGN 23 records)
+template <typename T, int N>
+static bool bundle_runs_two_pass(const tcfd_ns2d_plan* p) {
+    return bundle_two_pass<T, N>() || p->tune.bundle_rows == 0;
+}
+
+template <typename T, int N>
+static int launch_rows_jvp_bundle(const tcfd_ns2d_plan* p, const BundleWs<T>& W, bool want_p, int ntan, long batch, hipStream_t st) {
+    if (bundle_runs_two_pass<T, N>(p)) {
+        JvpWs<T> J{};
+        J.planes = W.planes;
+        J.adv = W.adv;
+        J.plane_stride = W.plane_stride;
+        int rc;
+        if (want_p && (rc = launch_rows_jvp<T, N, 1>(p, J, batch, st))) return rc;
+        // PART = 2 reads the four planes of ONE tangent plane_stride apart: [tangent][plane] within the group here
+        for (int t = 0; t < ntan; ++t) {
+            J.dplanes = W.dplanes + (size_t)t * 4 * W.plane_stride;
+            J.dadv = W.dadv + (size_t)t * W.plane_stride;
+            if ((rc = launch_rows_jvp<T, N, 2>(p, J, batch, st))) return rc;
+        }
+        return 0;
+    }
+    if constexpr (!bundle_two_pass<T, N>()) {
+        constexpr int EPT = Cfg<T, N>::ROW_EPT;
+        using Gm = BundleGeom<T, N, EPT>;
+        auto kern = k_rows_jvp_bundle<T, N, EPT>;
+        static DevOnce lds_once;
+        if (int rc_ = set_lds(lds_once, kern, Gm::LDS_BYTES)) return rc_;
+        const long npairs = batch * (N / 2);
+        const int per_cu = (int)std::min<size_t>(16, (160 * 1024) / Gm::LDS_BYTES);   // workgroups a CU holds
+        const long blocks = rows_grid(p, (npairs + Gm::GROUPS - 1) / Gm::GROUPS, 2 * per_cu);
+        // A small problem has fewer row pairs than the device has workgroup slots, and a group folds its K tangents one after
+        // the other: the tangents are then cut into segments (blockIdx.y), each redoing the state's four transforms, until the
+        // slots are filled (256^2 x 2 fp64: 64 workgroups of 36 transforms -> 512 of 8).  The arithmetic of a member is the same
+        // in any segment, so the bits do not depend on the cut.
+        const long slots = 256L * per_cu;
+        const int segs = (int)std::max<long>(1, std::min<long>(ntan, slots / blocks));
+        ProfScope prof(p, 1, st);
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)segs), dim3(Gm::THREADS), Gm::LDS_BYTES, st, (const cx<T>*)W.planes,
+                           W.plane_stride, (const cx<T>*)W.dplanes, W.dplane_stride, W.plane_stride, want_p ? W.adv : nullptr,
+                           W.dadv, W.plane_stride, (const cx<T>*)p->tw, npairs, p->ldw, ntan);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+// w: batch fields; dw / out_df: ntan tangents of batch fields, in_ts / out_ts elements apart (caller layout, pitch m); out_f may be null
+template <typename T, int N>
+static int explicit_jvp_bundle_impl(const tcfd_ns2d_plan* p, const BundleWs<T>& W, const cx<T>* w, const cx<T>* dw, size_t in_ts,
+                                    cx<T>* out_f, cx<T>* out_df, size_t out_ts, long batch, int ntan, int kg, hipStream_t st) {
+    constexpr int CEPT = Cfg<T, N>::COL_EPT, COLS = Cfg<T, N>::COLS;
+    const bool TWO = bundle_runs_two_pass<T, N>(p);
+    const size_t tight = (size_t)batch * N * p->m;                           // tangents one after the other, caller layout
+    const bool ws_tight = W.plane_stride == (size_t)batch * N * p->ldw;     // a field's scratch is not padded
+    int rc;
+    ColArgs<T> a{};
+    a.plane_stride = W.plane_stride;
+    a.u_in_ld = p->m;
+    a.nyq = 0;    // whole-column tiles, every column present (the row passes read the plain layout)
+    a.planes = W.planes;
+    a.u_in = w;
+    if ((rc = launch_cols_v<T, N, MODE_A, CEPT, COLS>(p, a, batch, st))) return rc;
+    for (int k0 = 0; k0 < ntan; k0 += kg) {
+        const int kn = std::min(kg, ntan - k0);
+        const bool first = (k0 == 0), want_p = first && out_f;
+        // the group's planes: [plane][tangent][field] (two-pass sizes: [tangent][plane][field], what k_rows_jvp reads)
+        a.plane_stride = TWO ? W.plane_stride : W.dplane_stride;
+        if (!TWO && ws_tight && in_ts == tight) {
+            a.planes = W.dplanes;
+            a.u_in = dw + (size_t)k0 * in_ts;
+            if ((rc = launch_cols_v<T, N, MODE_A, CEPT, COLS>(p, a, (long)kn * batch, st))) return rc;
+        } else {
+            for (int t = 0; t < kn; ++t) {
+                a.planes = W.dplanes + (size_t)t * (TWO ? 4 : 1) * W.plane_stride;
+                a.u_in = dw + (size_t)(k0 + t) * in_ts;
+                if ((rc = launch_cols_v<T, N, MODE_A, CEPT, COLS>(p, a, batch, st))) return rc;
+            }
+        }
+        if ((rc = launch_rows_jvp_bundle<T, N>(p, W, want_p, kn, batch, st))) return rc;
+        ColArgs<T> c{};
+        if (want_p) {
+            c.in = W.adv;
+            c.out = out_f;
+            if ((rc = launch_cols_v<T, N, MODE_F, CEPT, COLS>(p, c, batch, st))) return rc;
+        }
+        if (ws_tight && out_ts == tight) {
+            c.in = W.dadv;
+            c.out = out_df + (size_t)k0 * out_ts;
+            if ((rc = launch_cols_v<T, N, MODE_F, CEPT, COLS>(p, c, (long)kn * batch, st, /*no_forcing=*/true))) return rc;
+        } else {
+            for (int t = 0; t < kn; ++t) {
+                c.in = W.dadv + (size_t)t * W.plane_stride;
+                c.out = out_df + (size_t)(k0 + t) * out_ts;
+                if ((rc = launch_cols_v<T, N, MODE_F, CEPT, COLS>(p, c, batch, st, /*no_forcing=*/true))) return rc;
+            }
+        }
+    }
+    return 0;
+}
+
+// The stage update on the state (member 0) and on the K tangents (members 1 .. K) in one launch: k_stage_update_jvp's arithmetic,
+// member by member (blockIdx.y strides over the members).  Tangent arrays are `*_ts` elements apart.  Null hp / h as there; b may
+// be u (in place) -- no __restrict__ on the state and accumulator pointers.
+template <typename T>
+struct StageBundleArgs {
+    const cx<T>* f; const cx<T>* df; size_t df_ts;
+    const cx<T>* hp; const cx<T>* dhp;
+    const cx<T>* b; const cx<T>* db; size_t db_ts;
+    cx<T>* h; cx<T>* dh; size_t dh_ts;
+    cx<T>* u; cx<T>* du; size_t du_ts;
+    const T* Lt;
+    T fa, beta, gdt, mu, mud;
+    long total, plane;
+    int ntan;
+};
+template <typename T>
+__global__ __launch_bounds__(256) void k_stage_update_bundle(StageBundleArgs<T> a) {
+    for (int mem = blockIdx.y; mem <= a.ntan; mem += gridDim.y) {
+        const size_t k = mem ? (size_t)(mem - 1) : 0;
+        const cx<T>* f = mem ? a.df + k * a.df_ts : a.f;
+        const cx<T>* hp = !a.hp ? nullptr : (mem ? a.dhp + k * a.dh_ts : a.hp);
+        const cx<T>* b = mem ? a.db + k * a.db_ts : a.b;
+        cx<T>* h = !a.h ? nullptr : (mem ? a.dh + k * a.dh_ts : a.h);
+        cx<T>* u = mem ? a.du + k * a.du_ts : a.u;
+        for (long e = blockIdx.x * 256L + threadIdx.x; e < a.total; e += (long)gridDim.x * 256L) {
+            const T L = a.Lt[e % a.plane];
+            const T r = fast_rcp((T)1 - a.mud * L);
+            cx<T> hn = cscale(f[e], a.fa);
+            if (hp) hn = hn + cscale(hp[e], a.beta);
+            const cx<T> bv = b[e];
+            const cx<T> rhs = bv + cscale(hn, a.gdt) + cscale(cscale(bv, L), a.mu);
+            if (h) h[e] = hn;
+            u[e] = cscale(rhs, r);
+        }
+    }
+}
+
+template <typename T, int N>
+static int explicit_jvp_bundle_entry(const tcfd_ns2d_plan* p, const void* w, const void* dw, void* out_f, void* out_df,
+                                     size_t tan_stride, long batch, int ntan, int kg, void* ws, hipStream_t st) {
+    const BundleWs<T> W = carve_bundle<T>(p, ws, batch, ntan, kg);
+    return explicit_jvp_bundle_impl<T, N>(p, W, (const cx<T>*)w, (const cx<T>*)dw, tan_stride, (cx<T>*)out_f, (cx<T>*)out_df,
+                                          tan_stride, batch, ntan, kg, st);
+}
+
+// `steps` steps of the schedule of tcfd_ns2d_step_imex on the state and its K tangents: step_jvp_impl's sequencing, the tangent
+// buffers K deep.  dh_k starts from 0 every step, as h does.
+template <typename T, int N>
+static int step_jvp_bundle_impl(const tcfd_ns2d_plan* p, const void* w_in, const void* dw_in, void* w_out, void* dw_out,
+                                size_t tan_stride, long batch, int ntan, int kg, int nstages, const double* fa, const double* beta,
+                                const double* gdt, const double* mu, const double* mud, const int* base0, int steps, void* ws,
+                                hipStream_t st) {
+    const BundleWs<T> W = carve_bundle<T>(p, ws, batch, ntan, kg);
+    const long plane = (long)N * p->m, total = batch * plane;
+    const unsigned blocks = (unsigned)std::min<long>((total + 255) / 256, 1 << 16);
+    const unsigned members = (unsigned)std::min(ntan + 1, 1024);
+    const cx<T>* u_src = (const cx<T>*)w_in;
+    const cx<T>* du_src = (const cx<T>*)dw_in;
+    size_t du_ts = tan_stride;
+    for (int s = 0; s < steps; ++s) {
+        const cx<T>* u0 = u_src;
+        const cx<T>* du0 = du_src;
+        const size_t du0_ts = du_ts;
+        for (int k = 0; k < nstages; ++k) {
+            int rc;
+            if ((rc = explicit_jvp_bundle_impl<T, N>(p, W, u_src, du_src, du_ts, W.F, W.dF, W.tan_stride, batch, ntan, kg, st)))
+                return rc;
+            const bool last = (s == steps - 1) && (k == nstages - 1);
+            bool u0_needed_later = false;
+            for (int k2 = k + 1; k2 < nstages; ++k2) u0_needed_later |= (base0 && base0[k2]);
+            const bool from_u0 = base0 && base0[k];
+            int d = 0;
+            if (u0_needed_later && (const cx<T>*)W.s[0] == u0) d = 1;
+            const bool load_h = (k != 0), store_h = (k != nstages - 1);   // h starts from 0 every step
+            StageBundleArgs<T> a{};
+            a.f = W.F; a.df = W.dF; a.df_ts = W.tan_stride;
+            a.hp = load_h ? W.h : nullptr; a.dhp = W.dh;
+            a.b = from_u0 ? u0 : u_src; a.db = from_u0 ? du0 : du_src; a.db_ts = from_u0 ? du0_ts : du_ts;
+            a.h = store_h ? W.h : nullptr; a.dh = W.dh; a.dh_ts = W.tan_stride;
+            a.u = last ? (cx<T>*)w_out : W.s[d];
+            a.du = last ? (cx<T>*)dw_out : W.ds[d];
+            a.du_ts = last ? tan_stride : W.tan_stride;
+            a.Lt = (const T*)p->lin;
+            a.fa = fa ? (T)fa[k] : (T)1; a.beta = (T)beta[k]; a.gdt = (T)gdt[k]; a.mu = (T)mu[k]; a.mud = mud ? (T)mud[k] : (T)mu[k];
+            a.total = total; a.plane = plane; a.ntan = ntan;
+            hipLaunchKernelGGL(k_stage_update_bundle<T>, dim3(blocks, members), dim3(256), 0, st, a);
+            HIP_TRY(hipGetLastError());
+            u_src = a.u;
+            du_src = a.du;
+            du_ts = a.du_ts;
+        }
+    }
+    return 0;
+}
+
 // ------------------------------------------------------------------ adjoint model (reverse of the fused step)
 // Reverse of stage k of the schedule, everything that is element-wise (the transposes of k_stage_update, of the `g * pre`
 // weighting and of the additions autograd performs between its nodes), one launch:
@@ -2313,6 +2640,22 @@ int step_jvp(const tcfd_ns2d_plan* p, const void* w_in, const void* dw_in, void*
     });
 }
 template <typename T>
+int explicit_jvp_bundle(const tcfd_ns2d_plan* p, const void* w, const void* dw, void* out_f, void* out_df, size_t tan_stride,
+                        long batch, int ntan, int kg, void* ws, hipStream_t st) {
+    return by_size(p->n, [&](auto N) {
+        return explicit_jvp_bundle_entry<T, N()>(p, w, dw, out_f, out_df, tan_stride, batch, ntan, kg, ws, st);
+    });
+}
+template <typename T>
+int step_jvp_bundle(const tcfd_ns2d_plan* p, const void* w_in, const void* dw_in, void* w_out, void* dw_out, size_t tan_stride,
+                    long batch, int ntan, int kg, int nstages, const double* fa, const double* beta, const double* gdt,
+                    const double* mu_num, const double* mu_den, const int* base0, int steps, void* ws, hipStream_t st) {
+    return by_size(p->n, [&](auto N) {
+        return step_jvp_bundle_impl<T, N()>(p, w_in, dw_in, w_out, dw_out, tan_stride, batch, ntan, kg, nstages, fa, beta, gdt,
+                                            mu_num, mu_den, base0, steps, ws, st);
+    });
+}
+template <typename T>
 int step_vjp(const tcfd_ns2d_plan* p, const void* saved, size_t saved_step_stride, const void* g_out, const void* pre,
              const void* post, void* g_in, long batch, int nstages, const double* fa, const double* beta, const double* gdt,
              const double* mu_num, const double* mu_den, const int* base0, int steps, void* ws, hipStream_t st) {
@@ -2349,6 +2692,8 @@ template decltype(explicit_terms<TCFD_REAL>) explicit_terms<TCFD_REAL>;
 template decltype(explicit_vjp<TCFD_REAL>) explicit_vjp<TCFD_REAL>;
 template decltype(explicit_jvp<TCFD_REAL>) explicit_jvp<TCFD_REAL>;
 template decltype(step_jvp<TCFD_REAL>) step_jvp<TCFD_REAL>;
+template decltype(explicit_jvp_bundle<TCFD_REAL>) explicit_jvp_bundle<TCFD_REAL>;
+template decltype(step_jvp_bundle<TCFD_REAL>) step_jvp_bundle<TCFD_REAL>;
 template decltype(step_vjp<TCFD_REAL>) step_vjp<TCFD_REAL>;
 template decltype(rfft2<TCFD_REAL>) rfft2<TCFD_REAL>;
 template decltype(irfft2<TCFD_REAL>) irfft2<TCFD_REAL>;

@@ -249,6 +249,54 @@ class _HipPlan:
         _lib.check(rc, "tcfd_ns2d_step_jvp")
         return out, dout
 
+    def bundle_workspace(self, batch: int, ntan: int) -> torch.Tensor:
+        """Scratch of the tangent-bundle calls (``tcfd_ns2d_bundle_workspace_bytes``): the same buffer as ``workspace``, grown."""
+        if not hasattr(self.lib, "tcfd_ns2d_step_jvp_bundle"):   # added without a new ABI number: a stale library loads, but lacks them
+            raise _lib.TcfdError(f"{_lib.LIB_PATH} was built before the tangent-bundle entry points (tcfd_ns2d_*_jvp_bundle) were "
+                                 "added: rebuild it with torch_cfd_amd._lib.build_library(force=True)")
+        need = self.lib.tcfd_ns2d_bundle_workspace_bytes(self.handle, batch, ntan)
+        if need == 0:
+            raise _lib.TcfdError(f"tcfd_ns2d_bundle_workspace_bytes: batch = {batch}, ntangents = {ntan} out of range")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def _prep_bundle(self, w, dW):
+        w, batch = self._prep(w)
+        ntan = int(dW.shape[0])
+        dW = dW.detach().to(self.cdtype).contiguous()
+        return w, dW, batch, ntan
+
+    def explicit_terms_jvp_bundle(self, w, dW):
+        """(F(w), [F'(w) dW[k]]) for the K tangents ``dW`` = (K,) + w.shape in one sweep (``tcfd_ns2d_explicit_terms_jvp_bundle``)."""
+        w, dW, batch, ntan = self._prep_bundle(w, dW)
+        f, df = torch.empty_like(w), torch.empty_like(dW)
+        if batch == 0 or ntan == 0:
+            return f, df
+        ws = self.bundle_workspace(batch, ntan)
+        with torch.cuda.device(self.device):
+            rc = self.lib.tcfd_ns2d_explicit_terms_jvp_bundle(self.handle, w.data_ptr(), dW.data_ptr(), f.data_ptr(), df.data_ptr(),
+                                                              batch, ntan, ws.data_ptr(), ws.numel(), self._stream())
+        _lib.check(rc, "tcfd_ns2d_explicit_terms_jvp_bundle")
+        return f, df
+
+    def step_jvp_bundle(self, w, dW, beta, gdt, mu, steps: int, fa=None, mu_den=None, base0=None):
+        """``steps`` steps of the schedule of ``step`` on the state and K tangents of it together (``tcfd_ns2d_step_jvp_bundle``)."""
+        w, dW, batch, ntan = self._prep_bundle(w, dW)
+        out, dout = torch.empty_like(w), torch.empty_like(dW)
+        if batch == 0 or ntan == 0:
+            return out, dout
+        ws = self.bundle_workspace(batch, ntan)
+        ints = (ctypes.c_int * len(beta))(*[int(v) for v in base0]) if base0 is not None else None
+        with torch.cuda.device(self.device):
+            rc = self.lib.tcfd_ns2d_step_jvp_bundle(
+                self.handle, w.data_ptr(), dW.data_ptr(), out.data_ptr(), dout.data_ptr(), batch, ntan, len(beta),
+                _lib.darray(fa) if fa is not None else None, _lib.darray(beta), _lib.darray(gdt), _lib.darray(mu),
+                _lib.darray(mu_den) if mu_den is not None else None, ints, steps, ws.data_ptr(), ws.numel(), self._stream())
+        _lib.check(rc, "tcfd_ns2d_step_jvp_bundle")
+        return out, dout
+
     def step_vjp_workspace(self, batch: int, nstages: int) -> torch.Tensor:
         """Scratch of the adjoint model (``tcfd_ns2d_step_vjp_workspace_bytes``): the same buffer as ``workspace``, grown."""
         if not hasattr(self.lib, "tcfd_ns2d_step_vjp"):   # added without a new ABI number: a stale library loads, but lacks it
@@ -893,6 +941,47 @@ class NavierStokes2DSpectral(ImplicitExplicitODE):
         if self.solver is None:
             raise TypeError("NavierStokes2DSpectral needs a solver (e.g. RK4CrankNicolsonStepper()) to step")
         return self._tangent_steps(w_hat, dw_hat, dt, steps, self.solver.params, self.solver)
+
+    # -- K tangents per state in one call (tcfd_ns2d_explicit_terms_jvp_bundle / tcfd_ns2d_step_jvp_bundle)
+    def _bundle_plan(self, w_hat, dW_hat, what: str) -> _HipPlan:
+        """``_jvp_plan``'s checks, in its order, for a bundle ``dW_hat`` of shape ``(K,) + w_hat.shape``."""
+        self._refuse_ensemble(what)
+        if (not (torch.is_tensor(w_hat) and torch.is_tensor(dW_hat)) or dW_hat.dim() != w_hat.dim() + 1 or dW_hat.shape[0] < 1
+                or tuple(dW_hat.shape[1:]) != tuple(w_hat.shape) or dW_hat.dtype != w_hat.dtype or dW_hat.device != w_hat.device):
+            raise ValueError(f"{what}: the tangents must be (K,) + the state's shape with K >= 1, in its dtype and on its device, got "
+                             f"{tuple(getattr(dW_hat, 'shape', ()))} {getattr(dW_hat, 'dtype', None)} for "
+                             f"{tuple(getattr(w_hat, 'shape', ()))} {getattr(w_hat, 'dtype', None)}")
+        return self._jvp_plan(w_hat, dW_hat[0], what)   # (a member requires grad when the bundle does)
+
+    def explicit_terms_jvp_bundle(self, w_hat, dW_hat) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(F(w), dF)`` with ``dF[k] = F'(w) dW_hat[k]`` for a bundle of K tangents ``dW_hat`` of shape ``(K,) + w_hat.shape``
+        (same dtype and device): the state's transforms run once for all of them.  ``dF[k]`` is what
+        ``explicit_terms_jvp(w_hat, dW_hat[k])`` returns."""
+        f, df = self._bundle_plan(w_hat, dW_hat, "explicit_terms_jvp_bundle").explicit_terms_jvp_bundle(w_hat, dW_hat)
+        return f.reshape(w_hat.shape), df.reshape(dW_hat.shape)
+
+    def tangent_bundle_step(self, w_hat, dW_hat, dt, steps=1) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``steps`` steps of the operator's stepper on the state and on K perturbations of it: ``(w_new, dW_new)`` with
+        ``dW_new[k] = d(w_new)/d(w) . dW_hat[k]`` -- what K calls of ``tangent_step`` on the same state compute, with the
+        state's share of every stage done once (Lyapunov spectra and vectors, block Krylov, several Gauss-Newton directions).
+        ``dW_hat``: ``(K,) + w_hat.shape``, same dtype and device.  See ``orthonormalize_tangents`` for the QR step of
+        Benettin's method."""
+        if self.solver is None:
+            raise TypeError("NavierStokes2DSpectral needs a solver (e.g. RK4CrankNicolsonStepper()) to step")
+        what = "tangent_bundle_step"
+        plan = self._bundle_plan(w_hat, dW_hat, what)
+        stepper = self.solver
+        params = getattr(stepper, "params", {})      # (a foreign solver need not have any)
+        if self._wants_grad(*params.values()):
+            raise NotImplementedError(f"{what}: trainable stepper coefficients (requires_grad=True) together with a tangent "
+                                      "are not implemented; freeze the coefficients or step under torch.no_grad()")
+        if not _is_module_stepper(stepper):
+            raise NotImplementedError(f"{what}: the fused tangent-linear step needs a stepper of this module (IMEXStepper, "
+                                      "RK4CrankNicolsonStepper); a foreign solver differentiates through explicit_terms")
+        sc = self._schedule(stepper, params, dt)
+        out, dout = plan.step_jvp_bundle(w_hat, dW_hat, sc["beta"], sc["gdt"], sc["mu"], steps, fa=sc["fa"], mu_den=sc["mu_den"],
+                                         base0=sc["base0"])
+        return out.reshape(w_hat.shape), dout.reshape(dW_hat.shape)
 
     # -- reverse mode as an explicit call: the adjoint model on its own kernels (tcfd_ns2d_step_vjp), no autograd involved
     def adjoint_step(self, w_hat, g_hat, dt, steps=1, g_dwdt=None, checkpoint_every=1) -> Tuple[torch.Tensor, torch.Tensor]:
