@@ -61,7 +61,7 @@ def build_library(force: bool = False, verbose: bool = False, only=None) -> str:
     force = force or only is not None
     srcs = [os.path.join(CSRC, s) for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
     deps = srcs + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
-    deps += [os.path.join(INCLUDE, h) for h in ("tcfd.h", "tcfd_ns2d_adjoint.h", "tcfd_ns2d_bundle.h")]
+    deps += [os.path.join(INCLUDE, h) for h in ("tcfd.h", "tcfd_ns2d_adjoint.h", "tcfd_ns2d_bundle.h", "tcfd_ns2d_adjoint_bundle.h")]
     def fresh():
         return os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(d) for d in deps)
 
@@ -270,9 +270,19 @@ BUNDLE_SIGNATURES = {
                                        _sz, _vp]),
 }
 
+# name -> (restype, argtypes) of include/tcfd_ns2d_adjoint_bundle.h (K cotangents per trajectory in one adjoint call), mirrored one
+# to one
+COBUNDLE_SIGNATURES = {
+    "tcfd_ns2d_step_vjp_bundle_workspace_bytes": (_sz, [_vp, _l, _i, _i]),
+    "tcfd_ns2d_explicit_terms_vjp_bundle": (_i, [_vp, _vp, _vp, _vp, _l, _i, _vp, _sz, _vp]),
+    "tcfd_ns2d_step_vjp_bundle": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _dp, _dp, _dp, _dp, _dp, ctypes.POINTER(_i), _i,
+                                       _vp, _sz, _vp]),
+}
+
 
 def load() -> ctypes.CDLL:
-    """dlopen the library (once) and declare every prototype of include/tcfd.h, tcfd_ns2d_adjoint.h and tcfd_ns2d_bundle.h."""
+    """dlopen the library (once) and declare every prototype of include/tcfd.h, tcfd_ns2d_adjoint.h, tcfd_ns2d_bundle.h and
+    tcfd_ns2d_adjoint_bundle.h."""
     global _lib
     if _lib is not None:
         return _lib
@@ -289,7 +299,7 @@ def load() -> ctypes.CDLL:
         raise TcfdError(f"{LIB_PATH} has ABI revision {have}, this package expects {ABI_VERSION} (include/tcfd.h TCFD_ABI_VERSION): "
                         "rebuild it with `python -c 'import __graft_entry__ as g; g.build()'` after deleting the stale file, or "
                         "torch_cfd_amd._lib.build_library(force=True)")
-    for name, (res, args) in {**SIGNATURES, **ADJOINT_SIGNATURES, **BUNDLE_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **ADJOINT_SIGNATURES, **BUNDLE_SIGNATURES, **COBUNDLE_SIGNATURES}.items():
         if not hasattr(lib, name):
             continue  # optional symbol groups are checked by tests/test_abi.py against the header
         fn = getattr(lib, name)

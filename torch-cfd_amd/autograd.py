@@ -287,16 +287,19 @@ def _step_into(plan, src, dst, sched):
               base0=sched.get("base0"), out=dst)
 
 
-def _step_vjp(op, plan, saved, g, sched, out=None):
+def _step_vjp(op, plan, saved, g, sched, out=None, bundle=False):
     pre, post = FusedExplicitTerms._tables(op, plan, g.device)
-    return plan.step_vjp(saved, g, pre, post, sched["beta"], sched["gdt"], sched["mu"], fa=sched.get("fa"),
-                         mu_den=sched.get("mu_den"), base0=sched.get("base0"), out=out)
+    reverse = plan.step_vjp_bundle if bundle else plan.step_vjp
+    return reverse(saved, g, pre, post, sched["beta"], sched["gdt"], sched["mu"], fa=sched.get("fa"),
+                   mu_den=sched.get("mu_den"), base0=sched.get("base0"), out=out)
 
 
-def fused_steps_and_adjoint(op, plan, w, g, sched, steps, every=1):
+def fused_steps_and_adjoint(op, plan, w, g, sched, steps, every=1, bundle=False):
     """``(w_new, wbar)`` of ``steps`` fused steps from ``w`` (B, n, m) and the cotangent ``g`` of their result, without
     autograd: the fused forward step once per step into the saved buffer, then ``tcfd_ns2d_step_vjp``.  ``every = c > 1`` keeps
-    only the input of every c-th step and refills one segment of c saved states at a time from its checkpoint."""
+    only the input of every c-th step and refills one segment of c saved states at a time from its checkpoint.
+    ``bundle``: ``g`` is (K, B, n, m), K cotangents of the one trajectory -- the forward and every refill still run once, and
+    each segment is reversed for all K in one ``tcfd_ns2d_step_vjp_bundle`` call."""
     B = w.shape[0]
     w_new = torch.empty_like(w)
     if every <= 1 or steps <= 1:
@@ -304,7 +307,7 @@ def fused_steps_and_adjoint(op, plan, w, g, sched, steps, every=1):
         saved[0].copy_(w)
         for s in range(steps):
             _step_into(plan, saved[s], saved[s + 1] if s + 1 < steps else w_new, sched)
-        return w_new, _step_vjp(op, plan, saved, g, sched)
+        return w_new, _step_vjp(op, plan, saved, g, sched, bundle=bundle)
     every = min(every, steps)
     nseg = (steps + every - 1) // every
     ckpt = torch.empty((nseg,) + tuple(w.shape), dtype=w.dtype, device=w.device)
@@ -321,7 +324,7 @@ def fused_steps_and_adjoint(op, plan, w, g, sched, steps, every=1):
         seg[0].copy_(ckpt[j])
         for i in range(1, length):
             _step_into(plan, seg[i - 1], seg[i], sched)
-        _step_vjp(op, plan, seg[:length], wbar, sched, out=wbar)      # in place: g_in may alias g_out
+        _step_vjp(op, plan, seg[:length], wbar, sched, out=wbar, bundle=bundle)      # in place: g_in may alias g_out
     return w_new, wbar
 
 

@@ -16,6 +16,7 @@
 #include "tcfd_ns2d_plan.hpp"
 #include "../../include/tcfd_ns2d_adjoint.h"
 #include "../../include/tcfd_ns2d_bundle.h"
+#include "../../include/tcfd_ns2d_adjoint_bundle.h"
 
 using namespace tcfd;
 
@@ -731,6 +732,85 @@ extern "C" int tcfd_ns2d_step_vjp(const tcfd_ns2d_plan* p, const void* saved, co
         const size_t o = (size_t)b0 * esz;
         int rc = NS2D_SIZED(p, step_vjp, p, (const unsigned char*)saved + o, step_stride, (const unsigned char*)g_out + o, pre, post,
                             (unsigned char*)g_in + o, nb, nstages, fa, beta, gdt, mu_num, mu_den, base0, steps, ws, st);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------ adjoint model for a bundle of K cotangents per trajectory
+// Chunks and cotangent groups as the tangent bundle's (bundle_shape: the state's plane set and kg cotangent sets in flight are the
+// same cache budget); cobundle_fields chunk-sized fields, and never less than a call with fewer cotangents needs.
+extern "C" size_t tcfd_ns2d_step_vjp_bundle_workspace_bytes(const tcfd_ns2d_plan* p, long batch, int ncotangents, int nstages) {
+    if (!p || batch <= 0 || ncotangents < 1 || ncotangents > BUNDLE_MAX_TANGENTS || nstages <= 0 || nstages > VJP_MAX_STAGES) return 0;
+    size_t need = 0;
+    for (int k = 1; k <= ncotangents; ++k) {
+        const BundleShape lim = bundle_limits(p, batch, k);
+        need = std::max(need, (size_t)cobundle_fields(k, lim.kg, nstages) * field_bytes(p, lim.chunk));
+    }
+    return need;
+}
+
+// the checks the two cotangent-bundle calls share after their null checks
+static int check_cobundle(const tcfd_ns2d_plan* p, const char* what, long batch, int ncot, int nstages, void* ws, size_t ws_bytes) {
+    if (batch <= 0) return fail(TCFD_EINVAL, "%s: batch must be > 0", what);
+    if (ncot < 1 || ncot > BUNDLE_MAX_TANGENTS)
+        return fail(TCFD_EINVAL, "%s: ncotangents must be in [1, %d] (got %d)", what, BUNDLE_MAX_TANGENTS, ncot);
+    if (int rce = refuse_ensemble(p, what)) return rce;
+    if (nstages <= 0 || nstages > VJP_MAX_STAGES)
+        return fail(TCFD_EINVAL, "%s: nstages %d out of range [1, %d]", what, nstages, VJP_MAX_STAGES);
+    if (batch > max_batch(p) / ncot)
+        return fail(TCFD_EINVAL, "%s: batch %ld x %d cotangents exceeds the largest batch of one call at n = %d (%ld fields)", what,
+                    batch, ncot, p->n, max_batch(p));
+    return check_ws(p, batch, ws, ws_bytes, tcfd_ns2d_step_vjp_bundle_workspace_bytes(p, batch, ncot, nstages));
+}
+
+extern "C" int tcfd_ns2d_explicit_terms_vjp_bundle(const tcfd_ns2d_plan* p, const void* w, const void* gm, void* xout, long batch,
+                                                   int ncotangents, void* ws, size_t ws_bytes, void* stream) {
+    if (!p || !w || !gm || !xout) return fail(TCFD_EINVAL, "explicit_terms_vjp_bundle: null argument");
+    if (int rc = check_cobundle(p, "explicit_terms_vjp_bundle", batch, ncotangents, 1, ws, ws_bytes)) return rc;
+    const size_t esz = (p->dtype == TCFD_C128 ? 16 : 8) * (size_t)p->n * p->m;
+    const size_t sb = (size_t)batch * esz, cb = (size_t)ncotangents * sb;
+    // the groups of a chunk and the chunks of a call run one after the other: an output that overlapped an input would be read back
+    if (ranges_overlap(xout, 4 * cb, w, sb) || ranges_overlap(xout, 4 * cb, gm, cb))
+        return fail(TCFD_EINVAL, "explicit_terms_vjp_bundle: xout must not overlap w or gm");
+    hipStream_t st = (hipStream_t)stream;
+    const BundleShape sh = bundle_shape(p, batch, ncotangents);
+    const size_t cs = (size_t)batch * p->n * p->m;      // elements between two cotangents
+    for (long b0 = 0; b0 < batch; b0 += sh.chunk) {
+        const long nb = std::min(sh.chunk, batch - b0);
+        const size_t o = (size_t)b0 * esz;
+        int rc = NS2D_SIZED(p, explicit_vjp_bundle, p, (const unsigned char*)w + o, (const unsigned char*)gm + o,
+                            (unsigned char*)xout + o, cs, nb, ncotangents, sh.kg, ws, st);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+extern "C" int tcfd_ns2d_step_vjp_bundle(const tcfd_ns2d_plan* p, const void* saved, const void* g_out, const void* pre,
+                                         const void* post, void* g_in, long batch, int ncotangents, int nstages, const double* fa,
+                                         const double* beta, const double* gdt, const double* mu_num, const double* mu_den,
+                                         const int* base0, int steps, void* ws, size_t ws_bytes, void* stream) {
+    if (!p || !saved || !g_out || !pre || !post || !g_in || !beta || !gdt || !mu_num)
+        return fail(TCFD_EINVAL, "step_vjp_bundle: null argument");
+    if (steps <= 0) return fail(TCFD_EINVAL, "step_vjp_bundle: steps must be > 0 (got %d)", steps);
+    if (int rc = check_cobundle(p, "step_vjp_bundle", batch, ncotangents, nstages, ws, ws_bytes)) return rc;
+    const size_t esz = (p->dtype == TCFD_C128 ? 16 : 8) * (size_t)p->n * p->m;      // bytes of one field, caller layout
+    const size_t sb = (size_t)batch * esz, cb = (size_t)ncotangents * sb;
+    if (ranges_overlap(g_in, cb, saved, (size_t)steps * sb))
+        return fail(TCFD_EINVAL, "step_vjp_bundle: g_in overlaps saved (the saved states are read to the end)");
+    // g_in == g_out is in place (every chunk reads its own part of g_out first); a shifted overlap would let a later chunk read
+    // what an earlier one wrote
+    if (g_in != g_out && ranges_overlap(g_in, cb, g_out, cb))
+        return fail(TCFD_EINVAL, "step_vjp_bundle: g_in overlaps g_out without being g_out (identical or disjoint)");
+    hipStream_t st = (hipStream_t)stream;
+    const BundleShape sh = bundle_shape(p, batch, ncotangents);
+    const size_t cs = (size_t)batch * p->n * p->m;      // elements between saved[s] and saved[s + 1], and between two cotangents
+    for (long b0 = 0; b0 < batch; b0 += sh.chunk) {
+        const long nb = std::min(sh.chunk, batch - b0);
+        const size_t o = (size_t)b0 * esz;
+        int rc = NS2D_SIZED(p, step_vjp_bundle, p, (const unsigned char*)saved + o, cs, (const unsigned char*)g_out + o, pre, post,
+                            (unsigned char*)g_in + o, cs, nb, ncotangents, sh.kg, nstages, fa, beta, gdt, mu_num, mu_den, base0, steps,
+                            ws, st);
         if (rc) return rc;
     }
     return 0;

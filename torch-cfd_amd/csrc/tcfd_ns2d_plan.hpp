@@ -283,6 +283,56 @@ static VjpWs<T> carve_vjp(const tcfd_ns2d_plan* p, void* ws, long batch) {
     return w;
 }
 
+// Scratch of the adjoint model for a BUNDLE of K cotangents per trajectory (tcfd_ns2d_*_vjp_bundle): chunk-sized fields.  The
+// first 8 are `Ws` again (the recomputation runs explicit_impl on them; its planes then hold the state's planes of the reversed
+// stage), then the recomputed stage states, then what ONE GROUP of kg <= K cotangents needs in the sweep (nbar, the four Y planes,
+// the four X spectra), then what every cotangent carries from stage to stage: 7 + nstages + 9 kg + 4 K fields.
+// Y is stored [plane][cotangent][field] (`yplane_stride` per plane, `stride` per cotangent) and X likewise in the caller's pitch
+// (`xplane_stride` per plane, `tan_stride` per cotangent), so that ONE column launch over kg * batch fields fills nbar or drains a
+// plane of the group.  ubar, gm, hbar and ustart hold K cotangents of batch fields in the caller's pitch, `tan_stride` apart.
+static inline int cobundle_fields(int ncot, int kg, int nstages) { return 7 + nstages + 9 * kg + 4 * ncot; }
+template <typename T>
+struct CoBundleWs {
+    cx<T>* planes;        // Ws::planes: the state's four planes (plane 0 is F(u_k) while the stage states are recomputed)
+    cx<T>* hf[2];         // Ws::upad, Ws::upad2: the accumulator h of the recomputation
+    cx<T>* u;             // u_1 .. u_{nstages-1}, `stride` apart
+    cx<T>* nbar;          // kg: the column-transformed gm of the group
+    cx<T>* Y;             // 4 kg
+    cx<T>* X;             // 4 kg
+    cx<T>* ubar;          // K: the running cotangents of the state
+    cx<T>* gm;            // K: the pre-weighted cotangents of F
+    cx<T>* hbar;          // K: the cotangents of h
+    cx<T>* ustart;        // K: the cotangents of the step's initial state through the base0 stages
+    size_t stride;        // elements of one chunk-sized field
+    size_t yplane_stride; // kg * stride
+    size_t tan_stride;    // batch * n * m
+    size_t xplane_stride; // kg * tan_stride
+};
+template <typename T>
+static CoBundleWs<T> carve_cobundle(const tcfd_ns2d_plan* p, void* ws, long batch, int ncot, int kg, int nstages) {
+    const size_t fb = field_bytes(p, batch);
+    unsigned char* base = (unsigned char*)ws;
+    auto at = [&](long i) { return (cx<T>*)(base + (size_t)i * fb); };
+    CoBundleWs<T> w;
+    w.planes = at(2);
+    w.hf[0] = at(6);
+    w.hf[1] = at(7);
+    long i = 8;
+    w.u = at(i); i += nstages - 1;
+    w.nbar = at(i); i += kg;
+    w.Y = at(i); i += 4L * kg;
+    w.X = at(i); i += 4L * kg;
+    w.ubar = at(i); i += ncot;
+    w.gm = at(i); i += ncot;
+    w.hbar = at(i); i += ncot;
+    w.ustart = at(i);
+    w.stride = fb / sizeof(cx<T>);
+    w.yplane_stride = (size_t)kg * w.stride;
+    w.tan_stride = (size_t)batch * p->n * p->m;
+    w.xplane_stride = (size_t)kg * w.tan_stride;
+    return w;
+}
+
 // One stage of the schedule with constant coefficients, written exactly as the fused forward kernels write it (k_cols, MODE_C):
 //     h = fa f + beta h_prev ,    u = (b + gdt h + mu L b) / (1 - mud L)            (L: the real (n, m) linear term)
 // Launched by tcfd_ns2d_stage_update (the differentiable step of autograd.py) and by the recomputation of tcfd_ns2d_step_vjp.
@@ -358,6 +408,17 @@ template <typename T>
 int step_vjp(const tcfd_ns2d_plan* p, const void* saved, size_t saved_step_stride, const void* g_out, const void* pre,
              const void* post, void* g_in, long batch, int nstages, const double* fa, const double* beta, const double* gdt,
              const double* mu_num, const double* mu_den, const int* base0, int steps, void* ws, hipStream_t st);
+// one chunk of the cotangent-bundle calls: ncot cotangents per trajectory, kg of them per pass through the sweep; cot_stride:
+// elements between two cotangents of the caller's arrays (the whole call's batch * n * m); xout: plane f of cotangent k is
+// (4 k + f) cot_stride elements in
+template <typename T>
+int explicit_vjp_bundle(const tcfd_ns2d_plan* p, const void* w, const void* gm, void* xout, size_t cot_stride, long batch, int ncot,
+                        int kg, void* ws, hipStream_t st);
+template <typename T>
+int step_vjp_bundle(const tcfd_ns2d_plan* p, const void* saved, size_t saved_step_stride, const void* g_out, const void* pre,
+                    const void* post, void* g_in, size_t cot_stride, long batch, int ncot, int kg, int nstages, const double* fa,
+                    const double* beta, const double* gdt, const double* mu_num, const double* mu_den, const int* base0, int steps,
+                    void* ws, hipStream_t st);
 template <typename T> int rfft2(const tcfd_ns2d_plan* p, const void* x, void* out, long batch, hipStream_t st);
 template <typename T> int irfft2(const tcfd_ns2d_plan* p, const void* xh, void* out, long batch, void* ws, hipStream_t st);
 template <typename T> int irfft2_sub_max(const tcfd_ns2d_plan* p);

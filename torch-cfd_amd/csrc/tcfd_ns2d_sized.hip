@@ -1089,6 +1089,133 @@ __global__ __launch_bounds__((BundleGeom<T, N, EPT>::THREADS)) void k_rows_jvp_b
     }
 }
 
+// ---- row pass of a BUNDLE of cotangents: one state, K cotangents (the reverse-mode counterpart of k_rows_jvp_bundle) ----------
+// k_rows_vjp carries one cotangent per state, so K cotangents of one trajectory transform the state's four planes K times.  Here a
+// group transforms them ONCE per row pair into the stash of k_rows_jvp_bundle (same geometry, same slots: u, dxw, v, dyw from
+// planes 0, 2, 1, 3), then per cotangent k: one c2r of nbar_k, and four products  nbar_k x stash[s]  each followed by its r2c and
+// store into that cotangent's OWN plane set -- out of place, the state's planes must survive for the next cotangent group:
+//     Y0 = nbar dxw,  Y1 = nbar dyw,  Y2 = nbar u,  Y3 = nbar v             (k_rows_vjp's partner order)
+//     plane f of cotangent k  ->  yout + f * yplane_stride + k * ytan_stride
+// 4 + 5 K transforms per row pair instead of 9 K.  Live registers: nbar_k and the working array, two arrays of EPT elements.  The
+// cotangent loop and the four-product loop are NOT unrolled, for k_rows_jvp's reason.  Every member runs the same code on its own
+// data: member k has the bits of the K = 1 call whatever the other members hold, and whatever the cut of the cotangents into
+// blockIdx.y segments (each segment redoes the state's transforms; see the launcher).  Against k_rows_vjp the fp32 bits were equal
+// at every size tested and the fp64 bits differ in the last place (at most 4.0e-16 relative L2 of the four spectra, n = 8 .. 1536,
+// tests/test_ns2d_cobundle_gpu.py): hipcc contracts the multiply-adds of the transforms kernel by kernel, as for k_rows_jvp_bundle.
+template <typename T, int N, int EPT>
+__global__ __launch_bounds__((BundleGeom<T, N, EPT>::THREADS)) void k_rows_vjp_bundle(
+    const cx<T>* __restrict__ planes, size_t plane_stride, const cx<T>* __restrict__ nbar, size_t nbar_stride,
+    cx<T>* __restrict__ yout, size_t yplane_stride, size_t ytan_stride, const cx<T>* __restrict__ tw, long npairs, int ld, int ncot) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    using Gm = BundleGeom<T, N, EPT>;
+    constexpr int G = Gm::G;
+    constexpr bool WG = (G > 64);
+    constexpr int TH = Gm::THREADS;
+    const int grp = threadIdx.x / G;
+    const int j = threadIdx.x % G;
+    cx<T>* lds = reinterpret_cast<cx<T>*>(smem_raw) + (size_t)grp * Gm::XCH_PER_GROUP;
+    cx<T>* stash = reinterpret_cast<cx<T>*>(smem_raw) + (size_t)Gm::GROUPS * Gm::XCH_PER_GROUP + threadIdx.x;
+    const long stride = (long)gridDim.x * Gm::GROUPS;
+    long pair = (long)blockIdx.x * Gm::GROUPS + grp;
+    const long iters = (npairs + stride - 1) / stride;   // every group runs the same number of iterations (workgroup barriers)
+    const int kper = (ncot + (int)gridDim.y - 1) / (int)gridDim.y;
+    const int k_lo = (int)blockIdx.y * kper, k_hi = min(ncot, k_lo + kper);
+    for (long it = 0; it < iters; ++it, pair += stride) {
+        const bool valid = pair < npairs;
+        const long cur = valid ? pair : npairs - 1;
+        const size_t off = (size_t)cur * 2 * (size_t)ld;
+        cx<T> w[EPT], nb[EPT];
+        // the state: stash slot s = 0 .. 3 holds u, dxw, v, dyw (planes 0, 2, 1, 3)
+#pragma unroll 1
+        for (int s = 0; s < 4; ++s) {
+            const int f = (s & 1) ? 2 + (s >> 1) : (s >> 1);
+            const cx<T>* rowA = planes + (size_t)f * plane_stride + off;
+            {
+                RawPair<T, EPT> H;
+                load_raw<T, N, EPT>(H, rowA, rowA + ld, j);
+                pack_herm<T, N, EPT, WG>(w, H, lds, j);
+            }
+            tile_fft<T, N, EPT, +1, 1, true, WG>(w, lds, tw, j, 0);
+#pragma unroll
+            for (int t = 0; t < EPT; ++t) stash[(s * EPT + t) * TH] = w[t];
+        }
+#pragma unroll 1
+        for (int kt = k_lo; kt < k_hi; ++kt) {
+            {
+                const cx<T>* rowA = nbar + (size_t)kt * nbar_stride + off;
+                RawPair<T, EPT> H;
+                load_raw<T, N, EPT>(H, rowA, rowA + ld, j);
+                pack_herm<T, N, EPT, WG>(nb, H, lds, j);
+            }
+            tile_fft<T, N, EPT, +1, 1, true, WG>(nb, lds, tw, j, 0);
+            cx<T>* yset = yout + (size_t)kt * ytan_stride + off;
+            // stash slot s (u, dxw, v, dyw) is the partner of plane 2, 0, 3, 1
+#pragma unroll 1
+            for (int s = 0; s < 4; ++s) {
+                const int f = (s & 1) ? (s >> 1) : 2 + (s >> 1);
+#pragma unroll
+                for (int t = 0; t < EPT; ++t) {
+                    const cx<T> k = stash[(s * EPT + t) * TH];
+                    w[t] = mk<T>(nb[t].x * k.x, nb[t].y * k.y);
+                }
+                tile_fft<T, N, EPT, -1, 1, true, WG>(w, lds, tw, j, 0);
+                cx<T>* o = yset + (size_t)f * yplane_stride;
+                unpack_store_pair<T, N, EPT>(w, lds, o, o + ld, j, valid);
+            }
+        }
+    }
+}
+
+// The out-of-place form of k_rows_vjp for ONE cotangent: reads the state's planes and nbar (`gplane`), writes the four Y rows to
+// yout + f * yout_stride instead of over the planes -- the row pass of the cotangent bundle at the sizes whose stash does not fit
+// (bundle_two_pass), launched once per cotangent.  A kernel of its own: k_rows_vjp keeps its signature and its code.
+template <typename T, int N, int EPT, int THR>
+__global__ __launch_bounds__((RowGeom<T, N, EPT, THR>::THREADS)) void k_rows_vjp_oop(const cx<T>* __restrict__ planes,
+                                                                                     size_t plane_stride,
+                                                                                     const cx<T>* __restrict__ gplane,
+                                                                                     cx<T>* __restrict__ yout, size_t yout_stride,
+                                                                                     const cx<T>* __restrict__ tw, long npairs,
+                                                                                     int ld) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    using Gm = RowGeom<T, N, EPT, THR>;
+    constexpr int G = Gm::G;
+    constexpr bool WG = (G > 64);
+    const int grp = threadIdx.x / G;
+    const int j = threadIdx.x % G;
+    cx<T>* lds = reinterpret_cast<cx<T>*>(smem_raw) + (size_t)grp * Gm::LDS_PER_GROUP;
+    const long stride = (long)gridDim.x * Gm::GROUPS;
+    long pair = (long)blockIdx.x * Gm::GROUPS + grp;
+    const long iters = (npairs + stride - 1) / stride;   // every group runs the same number of iterations (workgroup barriers)
+    for (long it = 0; it < iters; ++it, pair += stride) {
+        const bool valid = pair < npairs;
+        const long cur = valid ? pair : npairs - 1;
+        const size_t off = (size_t)cur * 2 * (size_t)ld;
+        cx<T> nb[EPT], w[EPT];
+        {
+            RawPair<T, EPT> H;
+            load_raw<T, N, EPT>(H, gplane + off, gplane + off + ld, j);
+            pack_herm<T, N, EPT, WG>(nb, H, lds, j);
+        }
+        tile_fft<T, N, EPT, +1, 1, true, WG>(nb, lds, tw, j, 0);
+        // partner plane s of output plane f: dxw, dyw, u, v (planes 2, 3, 0, 1)
+#pragma unroll 1
+        for (int f = 0; f < 4; ++f) {
+            const cx<T>* rowA = planes + (size_t)(f ^ 2) * plane_stride + off;
+            {
+                RawPair<T, EPT> H;
+                load_raw<T, N, EPT>(H, rowA, rowA + ld, j);
+                pack_herm<T, N, EPT, WG>(w, H, lds, j);
+            }
+            tile_fft<T, N, EPT, +1, 1, true, WG>(w, lds, tw, j, 0);
+#pragma unroll
+            for (int t = 0; t < EPT; ++t) w[t] = mk<T>(nb[t].x * w[t].x, nb[t].y * w[t].y);
+            tile_fft<T, N, EPT, -1, 1, true, WG>(w, lds, tw, j, 0);
+            cx<T>* o = yout + (size_t)f * yout_stride + off;
+            unpack_store_pair<T, N, EPT>(w, lds, o, o + ld, j, valid);
+        }
+    }
+}
+
 // ---- row pass, one plane per transform ("v5") --------------------------------------------------
 // Round 1 rode two PLANES of one row through a complex transform, so the transformed velocity rows of BOTH rows of a pair
 // stayed live while the gradient planes were transformed (256 VGPR + 84 AGPR, one wave per SIMD at 1024^2 fp64; kernels v3 / v4,
@@ -2569,6 +2696,270 @@ static int step_vjp_impl(const tcfd_ns2d_plan* p, const void* saved, size_t save
     return 0;
 }
 
+// ------------------------------------------------------------------ cotangent bundle: one trajectory, K cotangents
+// The adjoint sweep of explicit_vjp_impl with the state's share done once: MODE_A on u_k (the caller: once per reversed stage),
+// then group by group (kg cotangents, bundle_shape in tcfd_ns2d.hip) MODE_INV on the group's gm, ONE row pass for the group
+// (k_rows_vjp_bundle, out of place: the state's planes serve every group), four MODE_FWD column transforms.  nbar is
+// [cotangent][field] and Y [plane][cotangent][field], so the column passes are single launches over kn * batch fields wherever the
+// arrays on both sides are tight; elsewhere they run per cotangent.  Sizes whose stash does not fit (bundle_two_pass, or
+// TCFD_BUNDLE_ROWS = 0) run k_rows_vjp_oop once per cotangent: the state's planes are read again, nothing else of the state repeats.
+template <typename T, int N>
+static int launch_rows_vjp_bundle(const tcfd_ns2d_plan* p, const CoBundleWs<T>& W, int ncot, long batch, hipStream_t st) {
+    const long npairs = batch * (N / 2);
+    if (bundle_runs_two_pass<T, N>(p)) {
+        constexpr int EPT = Cfg<T, N>::ROW_EPT, THR = Cfg<T, N>::ROW_THREADS;
+        using Gm = RowGeom<T, N, EPT, THR>;
+        auto kern = k_rows_vjp_oop<T, N, EPT, THR>;
+        static DevOnce lds_once;
+        if (int rc_ = set_lds(lds_once, kern, Gm::LDS_BYTES)) return rc_;
+        const long blocks = rows_grid(p, (npairs + Gm::GROUPS - 1) / Gm::GROUPS, 4);
+        for (int t = 0; t < ncot; ++t) {
+            ProfScope prof(p, 1, st);
+            hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(Gm::THREADS), Gm::LDS_BYTES, st, (const cx<T>*)W.planes, W.stride,
+                               (const cx<T>*)(W.nbar + (size_t)t * W.stride), W.Y + (size_t)t * W.stride, W.yplane_stride,
+                               (const cx<T>*)p->tw, npairs, p->ldw);
+            HIP_TRY(hipGetLastError());
+        }
+        return 0;
+    }
+    if constexpr (!bundle_two_pass<T, N>()) {
+        constexpr int EPT = Cfg<T, N>::ROW_EPT;
+        using Gm = BundleGeom<T, N, EPT>;
+        auto kern = k_rows_vjp_bundle<T, N, EPT>;
+        static DevOnce lds_once;
+        if (int rc_ = set_lds(lds_once, kern, Gm::LDS_BYTES)) return rc_;
+        const int per_cu = (int)std::min<size_t>(16, (160 * 1024) / Gm::LDS_BYTES);   // workgroups a CU holds
+        const long blocks = rows_grid(p, (npairs + Gm::GROUPS - 1) / Gm::GROUPS, 2 * per_cu);
+        // small problems: the cotangents are cut into segments until the device's workgroup slots are filled, as
+        // launch_rows_jvp_bundle cuts the tangents; the bits do not depend on the cut
+        const long slots = 256L * per_cu;
+        const int segs = (int)std::max<long>(1, std::min<long>(ncot, slots / blocks));
+        ProfScope prof(p, 1, st);
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)segs), dim3(Gm::THREADS), Gm::LDS_BYTES, st, (const cx<T>*)W.planes,
+                           W.stride, (const cx<T>*)W.nbar, W.stride, W.Y, W.yplane_stride, W.stride, (const cx<T>*)p->tw, npairs,
+                           p->ldw, ncot);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+// the opening column pass of the state of a reversed stage: u -> W.planes, once for every cotangent group
+template <typename T, int N>
+static int vjp_bundle_state(const tcfd_ns2d_plan* p, const CoBundleWs<T>& W, const cx<T>* u, long batch, hipStream_t st) {
+    ColArgs<T> a{};
+    a.planes = W.planes;
+    a.plane_stride = W.stride;
+    a.u_in = u;
+    a.u_in_ld = p->m;
+    a.nyq = 0;    // whole-column tiles, every column present (the row pass reads the plain layout)
+    return launch_cols_v<T, N, MODE_A, Cfg<T, N>::COL_EPT, Cfg<T, N>::COLS>(p, a, batch, st);
+}
+
+// one group of kn cotangents through the sweep; gm: kn fields of batch, gm_ts apart (caller layout, pitch m);
+// X_f of cotangent t -> xout + f * x_ps + t * x_ts (caller layout)
+template <typename T, int N>
+static int vjp_bundle_group(const tcfd_ns2d_plan* p, const CoBundleWs<T>& W, const cx<T>* gm, size_t gm_ts, cx<T>* xout, size_t x_ps,
+                            size_t x_ts, long batch, int kn, hipStream_t st) {
+    const size_t tight = (size_t)batch * N * p->m;                     // cotangents one after the other, caller layout
+    const bool ws_tight = W.stride == (size_t)batch * N * p->ldw;     // a field's scratch is not padded
+    int rc;
+    ColArgs<T> g{};
+    g.in_ld = p->m;
+    g.out_ld = p->ldw;
+    g.scale = (T)1;
+    if (ws_tight && gm_ts == tight) {
+        g.in = gm;
+        g.out = W.nbar;
+        if ((rc = launch_cols<T, N, MODE_INV>(p, g, (long)kn * batch, st))) return rc;
+    } else {
+        for (int t = 0; t < kn; ++t) {
+            g.in = gm + (size_t)t * gm_ts;
+            g.out = W.nbar + (size_t)t * W.stride;
+            if ((rc = launch_cols<T, N, MODE_INV>(p, g, batch, st))) return rc;
+        }
+    }
+    if ((rc = launch_rows_vjp_bundle<T, N>(p, W, kn, batch, st))) return rc;
+    ColArgs<T> c{};
+    c.in_ld = p->ldw;
+    c.out_ld = p->m;
+    c.scale = (T)1;
+    for (int f = 0; f < 4; ++f) {
+        if (ws_tight && x_ts == tight) {
+            c.in = W.Y + (size_t)f * W.yplane_stride;
+            c.out = xout + (size_t)f * x_ps;
+            if ((rc = launch_cols<T, N, MODE_FWD>(p, c, (long)kn * batch, st))) return rc;
+        } else {
+            for (int t = 0; t < kn; ++t) {
+                c.in = W.Y + (size_t)f * W.yplane_stride + (size_t)t * W.stride;
+                c.out = xout + (size_t)f * x_ps + (size_t)t * x_ts;
+                if ((rc = launch_cols<T, N, MODE_FWD>(p, c, batch, st))) return rc;
+            }
+        }
+    }
+    return 0;
+}
+
+template <typename T, int N>
+static int explicit_vjp_bundle_impl(const tcfd_ns2d_plan* p, const void* w, const void* gm, void* xout, size_t cot_stride, long batch,
+                                    int ncot, int kg, void* ws, hipStream_t st) {
+    const CoBundleWs<T> W = carve_cobundle<T>(p, ws, batch, ncot, kg, 1);
+    int rc;
+    if ((rc = vjp_bundle_state<T, N>(p, W, (const cx<T>*)w, batch, st))) return rc;
+    for (int k0 = 0; k0 < ncot; k0 += kg) {
+        const int kn = std::min(kg, ncot - k0);
+        if ((rc = vjp_bundle_group<T, N>(p, W, (const cx<T>*)gm + (size_t)k0 * cot_stride, cot_stride,
+                                         (cx<T>*)xout + (size_t)k0 * 4 * cot_stride, cot_stride, 4 * cot_stride, batch, kn, st)))
+            return rc;
+    }
+    return 0;
+}
+
+// k_stage_adjoint on K cotangents in one launch: the same arithmetic member by member (blockIdx.y strides over the members), one
+// L and one `pre` table.  ub is `ub_ts` apart per member (the caller's g_out at the first reversed stage of a call, ubar after),
+// every other array `ts`.  acc may be ub and hprev may be hb, as there -- no __restrict__ on them.
+template <typename T>
+struct StageAdjointBundleArgs {
+    const cx<T>* ub; size_t ub_ts;
+    const cx<T>* hb;
+    const T* Lt; const T* pre;
+    T fa, beta, gdt, mu, mud;
+    cx<T>* gm; cx<T>* hprev; cx<T>* acc; cx<T>* ustart;
+    int ustart_add;
+    size_t ts;
+    long total, plane;
+    int ncot;
+};
+template <typename T>
+__global__ __launch_bounds__(256) void k_stage_adjoint_bundle(StageAdjointBundleArgs<T> a) {
+    for (int mem = blockIdx.y; mem < a.ncot; mem += gridDim.y) {
+        const size_t o = (size_t)mem * a.ts;
+        const cx<T>* ub = a.ub ? a.ub + (size_t)mem * a.ub_ts : nullptr;
+        const cx<T>* hb = a.hb ? a.hb + o : nullptr;
+        cx<T>* gm = a.gm + o;
+        cx<T>* hprev = a.hprev ? a.hprev + o : nullptr;
+        cx<T>* acc = a.acc + o;
+        cx<T>* ustart = a.ustart ? a.ustart + o : nullptr;
+        for (long e = blockIdx.x * 256L + threadIdx.x; e < a.total; e += (long)gridDim.x * 256L) {
+            const long t = e % a.plane;
+            const T L = a.Lt[t];
+            cx<T> g = mk<T>((T)0, (T)0);
+            if (ub) g = cscale(ub[e], fast_rcp((T)1 - a.mud * L));
+            cx<T> G = cscale(g, a.gdt);
+            if (hb) G = G + hb[e];
+            gm[e] = cscale(cscale(G, a.fa), a.pre[t]);
+            if (hprev) hprev[e] = cscale(G, a.beta);
+            const cx<T> bb = g + cscale(cscale(g, L), a.mu);
+            if (ustart) {
+                ustart[e] = a.ustart_add ? ustart[e] + bb : bb;
+                acc[e] = mk<T>((T)0, (T)0);
+            } else {
+                acc[e] = bb;
+            }
+        }
+    }
+}
+
+// k_vjp_close on the members of one cotangent group in one launch: acc / extra `ts` apart per member, X `x_ts`, out `out_ts`
+// (the caller's g_in at the last reversed stage of a call).  out may be acc.
+template <typename T>
+struct VjpCloseBundleArgs {
+    const cx<T>* acc; const cx<T>* extra; size_t ts;
+    const cx<T>* X; size_t x_stride, x_ts;
+    const cx<T>* post;
+    cx<T>* out; size_t out_ts;
+    long total, plane;
+    int ncot;
+};
+template <typename T>
+__global__ __launch_bounds__(256) void k_vjp_close_bundle(VjpCloseBundleArgs<T> a) {
+    for (int mem = blockIdx.y; mem < a.ncot; mem += gridDim.y) {
+        const cx<T>* acc = a.acc + (size_t)mem * a.ts;
+        const cx<T>* extra = a.extra ? a.extra + (size_t)mem * a.ts : nullptr;
+        const cx<T>* X = a.X + (size_t)mem * a.x_ts;
+        cx<T>* out = a.out + (size_t)mem * a.out_ts;
+        for (long e = blockIdx.x * 256L + threadIdx.x; e < a.total; e += (long)gridDim.x * 256L) {
+            const long t = e % a.plane;
+            cx<T> s = mk<T>((T)0, (T)0);
+#pragma unroll
+            for (int f = 0; f < 4; ++f) {
+                const cx<T> x = X[(size_t)f * a.x_stride + e], q = a.post[(long)f * a.plane + t];
+                s = s + mk<T>(x.x * q.x - x.y * q.y, x.x * q.y + x.y * q.x);
+            }
+            s = acc[e] + s;
+            if (extra) s = s + extra[e];
+            out[e] = s;
+        }
+    }
+}
+
+// step_vjp_impl for K cotangents of one trajectory: the stage states are recomputed ONCE per step, MODE_A runs ONCE per reversed
+// stage, the element-wise kernels carry all K members, and the cotangents pass through the adjoint sweep group by group.
+// g_out / g_in: K cotangents of batch fields, cot_stride apart.
+template <typename T, int N>
+static int step_vjp_bundle_impl(const tcfd_ns2d_plan* p, const void* saved, size_t saved_step_stride, const void* g_out,
+                                const void* pre, const void* post, void* g_in, size_t cot_stride, long batch, int ncot, int kg,
+                                int nstages, const double* fa, const double* beta, const double* gdt, const double* mu,
+                                const double* mud, const int* base0, int steps, void* ws, hipStream_t st) {
+    const CoBundleWs<T> V = carve_cobundle<T>(p, ws, batch, ncot, kg, nstages);
+    const long plane = (long)N * p->m, total = batch * plane;
+    const unsigned blocks = (unsigned)std::min<long>((total + 255) / 256, 1 << 16);
+    const T* lin = (const T*)p->lin;
+    auto c = [&](const double* v, int k, double dflt) { return v ? (T)v[k] : (T)dflt; };
+    cx<T>* F = V.planes;     // plane 0: free once the row pass of the recomputation has run
+    const cx<T>* ub = (const cx<T>*)g_out;
+    size_t ub_ts = cot_stride;
+    int rc;
+    for (int s = steps - 1; s >= 0; --s) {
+        const cx<T>* u0 = (const cx<T>*)saved + (size_t)s * saved_step_stride;
+        auto state = [&](int k) { return k == 0 ? u0 : (const cx<T>*)(V.u + (size_t)(k - 1) * V.stride); };
+        auto from_u0 = [&](int k) { return k > 0 && base0 && base0[k]; };    // (at k = 0 the initial state IS the current one)
+        for (int k = 0; k + 1 < nstages; ++k) {
+            if ((rc = explicit_impl<T, N>(p, state(k), F, nullptr, nullptr, false, batch, ws, st, 0))) return rc;
+            hipLaunchKernelGGL(k_stage_update<T>, dim3(blocks), dim3(256), 0, st, (const cx<T>*)F,
+                               k ? (const cx<T>*)V.hf[(k - 1) & 1] : nullptr, from_u0(k) ? u0 : state(k), lin, c(fa, k, 1),
+                               (T)beta[k], (T)gdt[k], (T)mu[k], c(mud, k, mu[k]), V.hf[k & 1],
+                               V.u + (size_t)k * V.stride, total, plane);
+            HIP_TRY(hipGetLastError());
+        }
+        bool ustart_live = false;
+        for (int k = nstages - 1; k >= 0; --k) {
+            StageAdjointBundleArgs<T> a{};
+            a.ub = ub; a.ub_ts = ub_ts;
+            a.hb = k == nstages - 1 ? nullptr : (const cx<T>*)V.hbar;
+            a.Lt = lin; a.pre = (const T*)pre;
+            a.fa = c(fa, k, 1); a.beta = (T)beta[k]; a.gdt = (T)gdt[k]; a.mu = (T)mu[k]; a.mud = c(mud, k, mu[k]);
+            a.gm = V.gm; a.hprev = k ? V.hbar : nullptr; a.acc = V.ubar;
+            a.ustart = from_u0(k) ? V.ustart : nullptr; a.ustart_add = ustart_live ? 1 : 0;
+            a.ts = V.tan_stride; a.total = total; a.plane = plane; a.ncot = ncot;
+            hipLaunchKernelGGL(k_stage_adjoint_bundle<T>, dim3(blocks, (unsigned)std::min(ncot, 1024)), dim3(256), 0, st, a);
+            HIP_TRY(hipGetLastError());
+            ustart_live |= from_u0(k);
+            ub = V.ubar;
+            ub_ts = V.tan_stride;
+            if ((rc = vjp_bundle_state<T, N>(p, V, state(k), batch, st))) return rc;
+            const bool final = (s == 0 && k == 0);
+            for (int k0 = 0; k0 < ncot; k0 += kg) {
+                const int kn = std::min(kg, ncot - k0);
+                if ((rc = vjp_bundle_group<T, N>(p, V, V.gm + (size_t)k0 * V.tan_stride, V.tan_stride, V.X, V.xplane_stride,
+                                                 V.tan_stride, batch, kn, st)))
+                    return rc;
+                VjpCloseBundleArgs<T> cl{};
+                cl.acc = V.ubar + (size_t)k0 * V.tan_stride;
+                cl.extra = (k == 0 && ustart_live) ? V.ustart + (size_t)k0 * V.tan_stride : nullptr;
+                cl.ts = V.tan_stride;
+                cl.X = V.X; cl.x_stride = V.xplane_stride; cl.x_ts = V.tan_stride;
+                cl.post = (const cx<T>*)post;
+                cl.out = final ? (cx<T>*)g_in + (size_t)k0 * cot_stride : V.ubar + (size_t)k0 * V.tan_stride;
+                cl.out_ts = final ? cot_stride : V.tan_stride;
+                cl.total = total; cl.plane = plane; cl.ncot = kn;
+                hipLaunchKernelGGL(k_vjp_close_bundle<T>, dim3(blocks, (unsigned)std::min(kn, 1024)), dim3(256), 0, st, cl);
+                HIP_TRY(hipGetLastError());
+            }
+        }
+    }
+    return 0;
+}
+
 template <typename T, int N>
 static int irfft2_sub_max_impl(const tcfd_ns2d_plan*) {
     using Gm = RowGeom<T, N, Cfg<T, N>::ROW_EPT>;
@@ -2665,6 +3056,23 @@ int step_vjp(const tcfd_ns2d_plan* p, const void* saved, size_t saved_step_strid
     });
 }
 template <typename T>
+int explicit_vjp_bundle(const tcfd_ns2d_plan* p, const void* w, const void* gm, void* xout, size_t cot_stride, long batch, int ncot,
+                        int kg, void* ws, hipStream_t st) {
+    return by_size(p->n, [&](auto N) {
+        return explicit_vjp_bundle_impl<T, N()>(p, w, gm, xout, cot_stride, batch, ncot, kg, ws, st);
+    });
+}
+template <typename T>
+int step_vjp_bundle(const tcfd_ns2d_plan* p, const void* saved, size_t saved_step_stride, const void* g_out, const void* pre,
+                    const void* post, void* g_in, size_t cot_stride, long batch, int ncot, int kg, int nstages, const double* fa,
+                    const double* beta, const double* gdt, const double* mu_num, const double* mu_den, const int* base0, int steps,
+                    void* ws, hipStream_t st) {
+    return by_size(p->n, [&](auto N) {
+        return step_vjp_bundle_impl<T, N()>(p, saved, saved_step_stride, g_out, pre, post, g_in, cot_stride, batch, ncot, kg, nstages,
+                                            fa, beta, gdt, mu_num, mu_den, base0, steps, ws, st);
+    });
+}
+template <typename T>
 int rfft2(const tcfd_ns2d_plan* p, const void* x, void* out, long batch, hipStream_t st) {
     return by_size(p->n, [&](auto N) { return rfft2_impl<T, N()>(p, x, out, batch, st); });
 }
@@ -2695,6 +3103,8 @@ template decltype(step_jvp<TCFD_REAL>) step_jvp<TCFD_REAL>;
 template decltype(explicit_jvp_bundle<TCFD_REAL>) explicit_jvp_bundle<TCFD_REAL>;
 template decltype(step_jvp_bundle<TCFD_REAL>) step_jvp_bundle<TCFD_REAL>;
 template decltype(step_vjp<TCFD_REAL>) step_vjp<TCFD_REAL>;
+template decltype(explicit_vjp_bundle<TCFD_REAL>) explicit_vjp_bundle<TCFD_REAL>;
+template decltype(step_vjp_bundle<TCFD_REAL>) step_vjp_bundle<TCFD_REAL>;
 template decltype(rfft2<TCFD_REAL>) rfft2<TCFD_REAL>;
 template decltype(irfft2<TCFD_REAL>) irfft2<TCFD_REAL>;
 template decltype(irfft2_sub_max<TCFD_REAL>) irfft2_sub_max<TCFD_REAL>;

@@ -337,6 +337,66 @@ class _HipPlan:
         _lib.check(rc, "tcfd_ns2d_step_vjp")
         return out
 
+    def step_vjp_bundle_workspace(self, batch: int, ncot: int, nstages: int) -> torch.Tensor:
+        """Scratch of the cotangent-bundle calls (``tcfd_ns2d_step_vjp_bundle_workspace_bytes``): the same buffer as
+        ``workspace``, grown."""
+        if not hasattr(self.lib, "tcfd_ns2d_step_vjp_bundle"):   # added without a new ABI number: a stale library loads, but lacks them
+            raise _lib.TcfdError(f"{_lib.LIB_PATH} was built before the cotangent-bundle entry points (tcfd_ns2d_*_vjp_bundle) were "
+                                 "added: rebuild it with torch_cfd_amd._lib.build_library(force=True)")
+        need = self.lib.tcfd_ns2d_step_vjp_bundle_workspace_bytes(self.handle, batch, ncot, nstages)
+        if need == 0:
+            raise _lib.TcfdError(f"tcfd_ns2d_step_vjp_bundle_workspace_bytes: batch = {batch}, ncotangents = {ncot}, nstages = "
+                                 f"{nstages} out of range")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def explicit_terms_vjp_bundle(self, w, GM):
+        """``explicit_terms_vjp`` for K pre-weighted cotangents ``GM`` = (K,) + w.shape of one state in one sweep
+        (``tcfd_ns2d_explicit_terms_vjp_bundle``): shape (K, 4, *w.shape)."""
+        w, batch = self._prep(w)
+        GM, _ = self._prep(GM)
+        ncot = int(GM.shape[0])
+        if tuple(GM.shape[1:]) != tuple(w.shape):
+            raise ValueError(f"explicit_terms_vjp_bundle: cotangents {tuple(GM.shape)} for the state {tuple(w.shape)}")
+        out = torch.empty((ncot, 4) + tuple(w.shape), dtype=w.dtype, device=w.device)
+        if batch == 0 or ncot == 0:
+            return out
+        ws = self.step_vjp_bundle_workspace(batch, ncot, 1)
+        with torch.cuda.device(self.device):
+            rc = self.lib.tcfd_ns2d_explicit_terms_vjp_bundle(self.handle, w.data_ptr(), GM.data_ptr(), out.data_ptr(), batch, ncot,
+                                                              ws.data_ptr(), ws.numel(), self._stream())
+        _lib.check(rc, "tcfd_ns2d_explicit_terms_vjp_bundle")
+        return out
+
+    def step_vjp_bundle(self, saved, G_out, pre, post, beta, gdt, mu, fa=None, mu_den=None, base0=None, out=None):
+        """``step_vjp`` for K cotangents ``G_out`` (K, B, n, m) of the last result of the same ``saved`` (steps, B, n, m) in one
+        call (``tcfd_ns2d_step_vjp_bundle``): returns the K cotangents of ``saved[0]`` (written into ``out`` when given; ``out``
+        may be ``G_out``)."""
+        if saved.dim() != 4 or saved.dtype != self.cdtype or not saved.is_contiguous():
+            raise ValueError(f"step_vjp_bundle: expected a contiguous (steps, B, {self.n}, {self.m}) {self.cdtype} buffer of saved states")
+        G_out, _ = self._prep(G_out)
+        steps, batch = saved.shape[0], saved.shape[1]
+        if G_out.dim() != 4 or tuple(G_out.shape[1:]) != tuple(saved.shape[1:]):
+            raise ValueError(f"step_vjp_bundle: saved {tuple(saved.shape)} does not match the cotangents {tuple(G_out.shape)}")
+        ncot = int(G_out.shape[0])
+        if out is None:
+            out = torch.empty_like(G_out)
+        elif out.dtype != self.cdtype or out.shape != G_out.shape or not out.is_contiguous():
+            raise ValueError("step_vjp_bundle: `out` must be a contiguous tensor of the cotangents' shape and dtype")
+        if batch == 0 or ncot == 0:
+            return out
+        ws = self.step_vjp_bundle_workspace(batch, ncot, len(beta))
+        ints = (ctypes.c_int * len(beta))(*[int(v) for v in base0]) if base0 is not None else None
+        with torch.cuda.device(self.device):
+            rc = self.lib.tcfd_ns2d_step_vjp_bundle(
+                self.handle, saved.data_ptr(), G_out.data_ptr(), pre.data_ptr(), post.data_ptr(), out.data_ptr(), batch, ncot,
+                len(beta), _lib.darray(fa) if fa is not None else None, _lib.darray(beta), _lib.darray(gdt), _lib.darray(mu),
+                _lib.darray(mu_den) if mu_den is not None else None, ints, steps, ws.data_ptr(), ws.numel(), self._stream())
+        _lib.check(rc, "tcfd_ns2d_step_vjp_bundle")
+        return out
+
     def stream_residual(self, w, wt, want_psi=True, want_res=True):
         w, batch = self._prep(w)
         wt_, _ = self._prep(wt)
@@ -943,15 +1003,16 @@ class NavierStokes2DSpectral(ImplicitExplicitODE):
         return self._tangent_steps(w_hat, dw_hat, dt, steps, self.solver.params, self.solver)
 
     # -- K tangents per state in one call (tcfd_ns2d_explicit_terms_jvp_bundle / tcfd_ns2d_step_jvp_bundle)
-    def _bundle_plan(self, w_hat, dW_hat, what: str) -> _HipPlan:
-        """``_jvp_plan``'s checks, in its order, for a bundle ``dW_hat`` of shape ``(K,) + w_hat.shape``."""
+    def _bundle_plan(self, w_hat, dW_hat, what: str, dual: str = "tangent", kernels: str = "tangent-linear") -> _HipPlan:
+        """``_jvp_plan``'s checks, in its order, for a bundle ``dW_hat`` of shape ``(K,) + w_hat.shape`` (of tangents, or of
+        cotangents with ``dual`` = "cotangent")."""
         self._refuse_ensemble(what)
         if (not (torch.is_tensor(w_hat) and torch.is_tensor(dW_hat)) or dW_hat.dim() != w_hat.dim() + 1 or dW_hat.shape[0] < 1
                 or tuple(dW_hat.shape[1:]) != tuple(w_hat.shape) or dW_hat.dtype != w_hat.dtype or dW_hat.device != w_hat.device):
-            raise ValueError(f"{what}: the tangents must be (K,) + the state's shape with K >= 1, in its dtype and on its device, got "
+            raise ValueError(f"{what}: the {dual}s must be (K,) + the state's shape with K >= 1, in its dtype and on its device, got "
                              f"{tuple(getattr(dW_hat, 'shape', ()))} {getattr(dW_hat, 'dtype', None)} for "
                              f"{tuple(getattr(w_hat, 'shape', ()))} {getattr(w_hat, 'dtype', None)}")
-        return self._jvp_plan(w_hat, dW_hat[0], what)   # (a member requires grad when the bundle does)
+        return self._jvp_plan(w_hat, dW_hat[0], what, dual=dual, kernels=kernels)   # (a member requires grad when the bundle does)
 
     def explicit_terms_jvp_bundle(self, w_hat, dW_hat) -> Tuple[torch.Tensor, torch.Tensor]:
         """``(F(w), dF)`` with ``dF[k] = F'(w) dW_hat[k]`` for a bundle of K tangents ``dW_hat`` of shape ``(K,) + w_hat.shape``
@@ -1027,6 +1088,54 @@ class NavierStokes2DSpectral(ImplicitExplicitODE):
         if g_dwdt is not None:
             wbar = wbar - gd
         return w_new.reshape(lead), wbar.reshape(lead)
+
+    # -- K cotangents per trajectory in one adjoint call (tcfd_ns2d_step_vjp_bundle)
+    def adjoint_bundle_step(self, w_hat, G_hat, dt, steps=1, g_dwdt=None, checkpoint_every=1) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``adjoint_step`` for a bundle of K cotangents ``G_hat`` of shape ``(K,) + w_hat.shape`` (same dtype and device):
+        returns ``(w_new, Wbar)`` with ``Wbar[k] = (d w_new / d w)^T G_hat[k]`` -- what K calls of ``adjoint_step`` on the same
+        state compute (singular vectors by block iteration on J^T J together with ``tangent_bundle_step``, sensitivities of
+        several observables, rows of a Jacobian).  The forward sweep runs once and the saved inputs (or checkpoints) are
+        filled once; each segment is reversed for all K cotangents in one library call, with the recomputation of the stage
+        states and the state's transforms done once.  ``g_dwdt``: optional ``(K,) + w_hat.shape``, folded in as
+        ``adjoint_step`` does.  The bits are the same for every ``checkpoint_every``."""
+        if self.solver is None:
+            raise TypeError("NavierStokes2DSpectral needs a solver (e.g. RK4CrankNicolsonStepper()) to step")
+        what = "adjoint_bundle_step"
+        steps, c = int(steps), int(checkpoint_every)
+        if steps < 1 or c < 1:
+            raise ValueError(f"{what}: steps and checkpoint_every must be >= 1, got {steps}, {checkpoint_every}")
+        if g_dwdt is not None and (not torch.is_tensor(g_dwdt) or not torch.is_tensor(G_hat) or g_dwdt.shape != G_hat.shape
+                                   or g_dwdt.dtype != G_hat.dtype):
+            raise ValueError(f"{what}: g_dwdt must have the shape and dtype of the cotangents")
+        plan = self._bundle_plan(w_hat, G_hat, what, dual="cotangent", kernels="adjoint")
+        if self._wants_grad(g_dwdt):
+            raise NotImplementedError(f"{what}: reverse mode over the adjoint model is not implemented -- g_dwdt requires grad "
+                                      "in grad mode; detach it or differentiate with the reverse-mode path alone")
+        stepper = self.solver
+        if not _is_module_stepper(stepper):
+            raise NotImplementedError(f"{what}: the fused adjoint model needs a stepper of this module (IMEXStepper, "
+                                      "RK4CrankNicolsonStepper); a foreign solver differentiates through explicit_terms")
+        params = stepper.params
+        if self._wants_grad(*params.values()):
+            raise NotImplementedError(f"{what}: trainable stepper coefficients (requires_grad=True) are not implemented in the "
+                                      "adjoint model; freeze the coefficients or differentiate forward() with autograd")
+        from . import autograd as ad
+
+        sc = self._schedule(stepper, params, dt)
+        lead = w_hat.shape
+        w = w_hat.detach().to(plan.cdtype).reshape(-1, plan.n, plan.m).contiguous()
+        K = G_hat.shape[0]
+        G = G_hat.detach().to(plan.cdtype).reshape((K,) + tuple(w.shape))
+        scale = 1.0 / (steps * dt)
+        if g_dwdt is not None:
+            gd = g_dwdt.detach().to(plan.cdtype).reshape(G.shape) * scale
+            G = G + gd
+        if w.shape[0] == 0:
+            return torch.empty_like(w).reshape(lead), torch.empty_like(G).reshape(G_hat.shape)
+        w_new, Wbar = ad.fused_steps_and_adjoint(self, plan, w, G, sc, steps, c, bundle=True)
+        if g_dwdt is not None:
+            Wbar = Wbar - gd
+        return w_new.reshape(lead), Wbar.reshape(G_hat.shape)
 
     def _fused_steps(self, vort_hat, dt, steps, params=None, want_dwdt=True, stepper=None):
         stepper = self.solver if stepper is None else stepper
