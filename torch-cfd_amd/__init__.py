@@ -24,7 +24,7 @@ from . import datasets, pipeline  # noqa: F401  (device-resident data sets, norm
 from .datasets import BatchLoader, SpatioTemporalDataset, SpatioTemporalDatasetFixedTime  # noqa: F401
 from .fvm import NavierStokes2DFVMProjection, PressureProjection, RKStepper, get_trajectory_fvm  # noqa: F401
 from . import fvm, interpolation  # noqa: F401  (fvm.advection / fvm.convect and the scheme descriptors)
-from .fvm import advection  # noqa: F401
+from .fvm import advection, orthonormalize_velocity_tangents  # noqa: F401
 from .spectral import (  # noqa: F401
     brick_wall_filter_2d,
     fft_mesh_2d,

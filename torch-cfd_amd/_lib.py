@@ -61,7 +61,8 @@ def build_library(force: bool = False, verbose: bool = False, only=None) -> str:
     force = force or only is not None
     srcs = [os.path.join(CSRC, s) for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
     deps = srcs + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
-    deps += [os.path.join(INCLUDE, h) for h in ("tcfd.h", "tcfd_ns2d_adjoint.h", "tcfd_ns2d_bundle.h", "tcfd_ns2d_adjoint_bundle.h")]
+    deps += [os.path.join(INCLUDE, h) for h in ("tcfd.h", "tcfd_ns2d_adjoint.h", "tcfd_ns2d_bundle.h", "tcfd_ns2d_adjoint_bundle.h",
+                                                 "tcfd_fvm_bundle.h")]
     def fresh():
         return os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(d) for d in deps)
 
@@ -279,10 +280,16 @@ COBUNDLE_SIGNATURES = {
                                        _vp, _sz, _vp]),
 }
 
+# name -> (restype, argtypes) of include/tcfd_fvm_bundle.h (K tangents per finite-volume state in one call), mirrored one to one
+FVM_BUNDLE_SIGNATURES = {
+    "tcfd_fvm_plan_set_tangent_bundle": (_i, [_vp, _i]),
+}
+TCFD_FVM_MAX_TANGENTS = 65534   # include/tcfd_fvm_bundle.h
+
 
 def load() -> ctypes.CDLL:
-    """dlopen the library (once) and declare every prototype of include/tcfd.h, tcfd_ns2d_adjoint.h, tcfd_ns2d_bundle.h and
-    tcfd_ns2d_adjoint_bundle.h."""
+    """dlopen the library (once) and declare every prototype of include/tcfd.h, tcfd_ns2d_adjoint.h, tcfd_ns2d_bundle.h,
+    tcfd_ns2d_adjoint_bundle.h and tcfd_fvm_bundle.h."""
     global _lib
     if _lib is not None:
         return _lib
@@ -299,7 +306,8 @@ def load() -> ctypes.CDLL:
         raise TcfdError(f"{LIB_PATH} has ABI revision {have}, this package expects {ABI_VERSION} (include/tcfd.h TCFD_ABI_VERSION): "
                         "rebuild it with `python -c 'import __graft_entry__ as g; g.build()'` after deleting the stale file, or "
                         "torch_cfd_amd._lib.build_library(force=True)")
-    for name, (res, args) in {**SIGNATURES, **ADJOINT_SIGNATURES, **BUNDLE_SIGNATURES, **COBUNDLE_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **ADJOINT_SIGNATURES, **BUNDLE_SIGNATURES, **COBUNDLE_SIGNATURES,
+                               **FVM_BUNDLE_SIGNATURES}.items():
         if not hasattr(lib, name):
             continue  # optional symbol groups are checked by tests/test_abi.py against the header
         fn = getattr(lib, name)

@@ -24,9 +24,15 @@
 // state kernel's own code and dk = J_F(u) du from the same stencil, and writes the RK targets of both halves.  Every other pass
 // (k_fvm_div, the transforms, k_fvm_mul, k_fvm_apply) is linear per field and runs unchanged over the 2 B fields.
 //
-// Ensemble plan (tcfd_fvm_plan_set_ensemble): sample b of a call runs with its own viscosity, drag and forcing amplitude.  The three
-// stage kernels (k_fvm_stage, k_fvm_stage_jvp, k_fvm_stage_vjp) have an EnsConst instantiation that reads the three values of
-// member blockIdx.z from a plan-owned table; every other pass reads no physics and runs unchanged.
+// Tangent bundle (a plan with tcfd_fvm_plan_set_tangent_bundle K, include/tcfd_fvm_bundle.h): every field array holds 1 + K fields
+// per sample, fields [0, B) the state and fields [(1 + k) B, (2 + k) B) perturbation k.  k_fvm_stage_jvp_bundle replaces
+// k_fvm_stage and runs over the B samples: the state's loads, explicit terms and the state-only share of every flux tangent once,
+// then the K members by k_fvm_stage_jvp's arithmetic (member k has the bits of a tangent plan on (u, du_k)).  Every other pass
+// runs unchanged over the (1 + K) B fields.
+//
+// Ensemble plan (tcfd_fvm_plan_set_ensemble): sample b of a call runs with its own viscosity, drag and forcing amplitude.  The
+// stage kernels (k_fvm_stage, k_fvm_stage_jvp, k_fvm_stage_jvp_bundle, k_fvm_stage_vjp) have an EnsConst instantiation that reads
+// the three values of member blockIdx.z from a plan-owned table; every other pass reads no physics and runs unchanged.
 //
 // Every arithmetic expression restates the reference's operation order; floating-point contraction is off in this file
 // so that a * b + c rounds twice as the reference's tensor ops do.
@@ -39,6 +45,7 @@
 #include <vector>
 
 #include "tcfd_host.hpp"
+#include "../../include/tcfd_fvm_bundle.h"
 
 #pragma clang fp contract(off)
 
@@ -486,6 +493,208 @@ __global__ void __launch_bounds__(256) k_fvm_stage_jvp(const T* __restrict__ ux,
     }
 }
 
+// ---------------------------------------------------------------- tangent bundle: K perturbations of one state
+// What tvd_flux_jvp / face_flux_jvp compute from the state alone, kept per face while the members of a bundle pass: the same
+// expressions in the same order, so a member's flux tangent has the bits of the pair kernel's.  UPWIND keeps the selected cell in
+// `ci`, LINEAR the interpolated one; the fields a scheme does not read are never formed.
+template <typename T>
+struct FaceState {
+    T w, d, ab, den, r, phi, cmh, ci;   // ab: alpha (w > 0) or beta;  cmh: clow - chigh
+    bool pos, dnz, lim;
+};
+
+template <int SCHEME, typename T>
+__device__ __forceinline__ FaceState<T> face_state(T cm, T c0, T c1, T c2, T w, T cfl) {
+    FaceState<T> f{};
+    f.w = w;
+    if constexpr (SCHEME == LINEAR) {
+        f.ci = half(c0, c1);
+    } else if constexpr (SCHEME == UPWIND) {
+        f.pos = w > T(0);
+        f.ci = f.pos ? c0 : c1;
+    } else {
+        f.pos = w > T(0);
+        const T cr = cfl * w;
+        f.d = c1 - c0;
+        const T alpha = T(0.5) * (T(1) - cr);
+        const T beta = T(0.5) * (T(1) + cr);
+        f.ab = f.pos ? alpha : beta;
+        const T chigh = f.pos ? c0 + alpha * f.d : c1 - beta * f.d;
+        if constexpr (SCHEME == LAX_WENDROFF) {
+            f.ci = chigh;
+        } else {
+            const T clow = f.pos ? c0 : c1;
+            f.dnz = f.d != T(0);
+            f.den = f.dnz ? f.d : T(1);
+            f.r = (f.pos ? c0 - cm : c2 - c1) / f.den;
+            f.lim = f.r > T(0);
+            const T rp1 = T(1) + f.r;
+            f.phi = f.lim ? (T(2) * f.r) / rp1 : T(0);
+            f.cmh = clow - chigh;
+            f.ci = clow - f.cmh * f.phi;
+        }
+    }
+    return f;
+}
+
+// the tangent of the face's flux along (dcm, dc0, dc1, dc2, dw): tvd_flux_jvp / face_flux_jvp with the state's share read from f
+template <int SCHEME, typename T>
+__device__ __forceinline__ T face_state_jvp(const FaceState<T>& f, T dcm, T dc0, T dc1, T dc2, T dw, T cfl) {
+    if constexpr (SCHEME == LINEAR) {
+        return half(dc0, dc1) * f.w + f.ci * dw;
+    } else if constexpr (SCHEME == UPWIND) {
+        return (f.pos ? dc0 : dc1) * f.w + f.ci * dw;
+    } else {
+        const T dd = dc1 - dc0;
+        const T dchigh = (f.pos ? dc0 + f.ab * dd : dc1 - f.ab * dd) - (T(0.5) * (cfl * dw)) * f.d;
+        if constexpr (SCHEME == LAX_WENDROFF) {
+            return dchigh * f.w + f.ci * dw;
+        } else {
+            const T dclow = f.pos ? dc0 : dc1;
+            const T dden = f.dnz ? dd : T(0);
+            const T dr = ((f.pos ? dc0 - dcm : dc2 - dc1) - f.r * dden) / f.den;
+            const T rp1 = T(1) + f.r;
+            const T dphi = f.lim ? (T(2) * dr - f.phi * dr) / rp1 : T(0);
+            const T dci = dclow - ((dclow - dchigh) * f.phi + f.cmh * dphi);
+            return dci * f.w + f.ci * dw;
+        }
+    }
+}
+
+// The stencil of ONE momentum component around cell (i, j): the transported component C along both axes and the two cells
+// behind each of its four face velocities.  COMP 0 is ux (its axis-0 faces move with ux itself, its axis-1 faces with uy), COMP 1
+// is uy (the other way round): the faces and arguments of explicit_point / explicit_point_jvp.  The two-cell schemes never form
+// the +-2 addresses.
+template <typename T>
+struct CompStencil {
+    T c00, cm1, cp1, cm2, cp2, cjm1, cjp1, cjm2, cjp2;
+    T fh_a, fh_b, fl_a, fl_b, gh_a, gh_b, gl_a, gl_b;
+};
+
+template <int COMP, int SCHEME, typename T>
+__device__ __forceinline__ CompStencil<T> comp_stencil(const T* __restrict__ C, const T* __restrict__ O, int i, int j, int n) {
+    auto at = [n](const T* p, int a, int b) { return p[(size_t)a * n + b]; };
+    const int im1 = wrap(i - 1, n), ip1 = wrap(i + 1, n);
+    const int jm1 = wrap(j - 1, n), jp1 = wrap(j + 1, n);
+    CompStencil<T> v{};
+    v.c00 = at(C, i, j);
+    v.cm1 = at(C, im1, j);
+    v.cp1 = at(C, ip1, j);
+    v.cjm1 = at(C, i, jm1);
+    v.cjp1 = at(C, i, jp1);
+    if constexpr (SCHEME == VAN_LEER) {
+        v.cm2 = at(C, wrap(i - 2, n), j);
+        v.cp2 = at(C, wrap(i + 2, n), j);
+        v.cjm2 = at(C, i, wrap(j - 2, n));
+        v.cjp2 = at(C, i, wrap(j + 2, n));
+    }
+    if constexpr (COMP == 0) {
+        v.fh_a = v.c00, v.fh_b = v.cp1;
+        v.fl_a = v.cm1, v.fl_b = v.c00;
+        v.gh_a = at(O, i, j), v.gh_b = at(O, ip1, j);
+        v.gl_a = at(O, i, jm1), v.gl_b = at(O, ip1, jm1);
+    } else {
+        v.fh_a = at(O, i, j), v.fh_b = at(O, i, jp1);
+        v.fl_a = at(O, im1, j), v.fl_b = at(O, im1, jp1);
+        v.gh_a = v.c00, v.gh_b = v.cjp1;
+        v.gl_a = v.cjm1, v.gl_b = v.c00;
+    }
+    return v;
+}
+
+// One momentum component of the K members of cell (i, j): the four faces' state shares once, then per member the tangent of
+// explicit_point_jvp's component -- its fluxes, the order of its sums, finish_point's Laplacian and drag on the perturbation, no
+// forcing -- and k_fvm_stage_jvp's target expressions.  U / U0 / K_OUT / tgp: this component's arrays; UO: the other component.
+template <int COMP, int SCHEME, typename T, typename S>
+__device__ __forceinline__ void bundle_component(const T* __restrict__ U, const T* __restrict__ UO, const T* __restrict__ U0,
+                                                 T* __restrict__ K_OUT, T* const* tgp, const Targets<T>& tg, const S& s, int i,
+                                                 int j, int n, size_t base, size_t tan_stride, int ntan) {
+    FaceState<T> f_hi, f_lo, g_hi, g_lo;
+    {
+        const CompStencil<T> v = comp_stencil<COMP, SCHEME>(U + base, UO + base, i, j, n);
+        f_hi = face_state<SCHEME>(v.cm1, v.c00, v.cp1, v.cp2, half(v.fh_a, v.fh_b), s.cfl);
+        f_lo = face_state<SCHEME>(v.cm2, v.cm1, v.c00, v.cp1, half(v.fl_a, v.fl_b), s.cfl);
+        g_hi = face_state<SCHEME>(v.cjm1, v.c00, v.cjp1, v.cjp2, half(v.gh_a, v.gh_b), s.cfl);
+        g_lo = face_state<SCHEME>(v.cjm2, v.cjm1, v.c00, v.cjp1, half(v.gl_a, v.gl_b), s.cfl);
+    }
+    const size_t p = base + (size_t)i * n + j;
+    for (int k = 0; k < ntan; ++k) {
+        const size_t off = (size_t)(k + 1) * tan_stride;
+        const CompStencil<T> d = comp_stencil<COMP, SCHEME>(U + off + base, UO + off + base, i, j, n);
+        const T t_fhi = face_state_jvp<SCHEME>(f_hi, d.cm1, d.c00, d.cp1, d.cp2, half(d.fh_a, d.fh_b), s.cfl);
+        const T t_flo = face_state_jvp<SCHEME>(f_lo, d.cm2, d.cm1, d.c00, d.cp1, half(d.fl_a, d.fl_b), s.cfl);
+        const T t_ghi = face_state_jvp<SCHEME>(g_hi, d.cjm1, d.c00, d.cjp1, d.cjp2, half(d.gh_a, d.gh_b), s.cfl);
+        const T t_glo = face_state_jvp<SCHEME>(g_lo, d.cjm2, d.cjm1, d.c00, d.cjp1, half(d.gl_a, d.gl_b), s.cfl);
+        const T dadv = -((t_fhi - t_flo) / s.h + (t_ghi - t_glo) / s.h);
+        // finish_point's component on the perturbation, without the forcing
+        T lap = (T(-2) * d.c00) * s.sum_s;
+        lap = lap + (d.cm1 + d.cp1) * s.inv_h2;
+        lap = lap + (d.cjm1 + d.cjp1) * s.inv_h2;
+        T dk = dadv + s.nu * lap;
+        if (s.drag_on) dk = dk + d.c00 * s.neg_drag;
+        const size_t dp = off + p;
+        if (K_OUT) K_OUT[dp] = dk;
+        for (int t = 0; t < tg.count; ++t) {
+            const int mode = tg.mode[t];
+            T v = mode == 2 ? tgp[t][dp] : U0[dp];
+            if (mode != 3) v = v + dk * tg.c[t];
+            tgp[t][dp] = v;
+        }
+    }
+}
+
+// k_fvm_stage_jvp for one state and its K = ntan perturbations: fields [0, B) of every array the state, fields
+// [(1 + k) B, (2 + k) B) tangent k, `tan_stride` = B n^2 elements apart (K = 1: the pair layout).  One thread per cell of the B
+// samples; blockIdx.z = sample; the thread walks the members, so nothing is summed across threads and two runs give the same
+// bits.  The state half is explicit_point and k_fvm_stage's target expressions: the bits of the plain kernel.  The members go
+// in two passes, the ux component of all K and then the uy component of all K, the two being independent down to their targets:
+// a pass holds the state shares of four faces, not eight, across its member loop.
+template <int SCHEME, typename T, typename S>
+__global__ void __launch_bounds__(256) k_fvm_stage_jvp_bundle(const T* __restrict__ ux, const T* __restrict__ uy,
+                                                              const T* __restrict__ u0x, const T* __restrict__ u0y,
+                                                              const T* __restrict__ fx, const T* __restrict__ fy,
+                                                              T* __restrict__ kx_out, T* __restrict__ ky_out, Targets<T> tg, S s,
+                                                              int n, size_t tan_stride, int ntan) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = blockIdx.y * blockDim.y + threadIdx.y;
+    if (i >= n || j >= n) return;
+    const size_t plane = (size_t)n * n;
+    const size_t base = (size_t)blockIdx.z * plane;
+    auto body = [&](const auto& c) {   // c: the constants of this sample (the plan's, or member blockIdx.z's for all 1 + K fields)
+        T kx, ky;
+        explicit_point<SCHEME>(ux + base, uy + base, fx, fy, i, j, n, c, kx, ky);
+        const size_t p = base + (size_t)i * n + j;
+        if (kx_out) {
+            kx_out[p] = kx;
+            ky_out[p] = ky;
+        }
+        for (int t = 0; t < tg.count; ++t) {
+            const int mode = tg.mode[t];
+            const T w = tg.c[t];
+            T px, py;
+            if (mode == 2) {
+                px = tg.x[t][p];
+                py = tg.y[t][p];
+            } else {
+                px = u0x[p];
+                py = u0y[p];
+            }
+            if (mode != 3) {
+                px = px + kx * w;
+                py = py + ky * w;
+            }
+            tg.x[t][p] = px;
+            tg.y[t][p] = py;
+        }
+        bundle_component<0, SCHEME>(ux, uy, u0x, kx_out, tg.x, tg, c, i, j, n, base, tan_stride, ntan);
+        bundle_component<1, SCHEME>(uy, ux, u0y, ky_out, tg.y, tg, c, i, j, n, base, tan_stride, ntan);
+    };
+    if constexpr (kEnsemble<S>)
+        body(member_const(s.plan, s.rows, blockIdx.z));
+    else
+        body(s);
+}
+
 // div = (ux - ux[i-1]) / h + (uy - uy[j-1]) / h  (finite_differences.py:116-135)
 template <typename T>
 __global__ void __launch_bounds__(256) k_fvm_div(const T* __restrict__ ux, const T* __restrict__ uy, T* __restrict__ div, T h, int n) {
@@ -822,6 +1031,7 @@ struct tcfd_fvm_plan {
     int tangent;               // 1: every call carries pairs, fields [0, B) the state and [B, 2 B) its perturbation
     void* ens;                 // per-sample physics (tcfd_fvm_plan_set_ensemble): ens_count x {nu / density, -drag, forcing scale}
     long ens_count;            //   in the field precision, or NULL / 0: a scalar plan, whose launches are what they always were
+    int bundle;                // K > 0: every call carries 1 + K fields per sample, the state and K perturbations of it (excludes tangent)
 };
 
 namespace {
@@ -849,6 +1059,13 @@ StageConst<T> stage_const(const tcfd_fvm_plan* p, double dt) {
 // again: row blockIdx.z of the table exists for every block they launch.
 int check_ensemble_batch(const tcfd_fvm_plan* p, long batch, const char* what) {
     if (p->ens_count <= 0) return 0;
+    if (p->bundle) {
+        if (batch != (1 + (long)p->bundle) * p->ens_count)
+            return FAIL(TCFD_EINVAL, "%s: batch %ld on a bundle plan of %d tangents with per-sample parameters for %ld members, which "
+                                     "takes (1 + %d) x %ld fields (tcfd_fvm_plan_set_ensemble)", what, batch, p->bundle, p->ens_count,
+                        p->bundle, p->ens_count);
+        return 0;
+    }
     if (p->tangent && batch != 2 * p->ens_count)
         return FAIL(TCFD_EINVAL, "%s: batch %ld on a tangent plan with per-sample parameters for %ld members, which takes 2 x %ld "
                                  "fields (tcfd_fvm_plan_set_ensemble)", what, batch, p->ens_count, p->ens_count);
@@ -858,10 +1075,26 @@ int check_ensemble_batch(const tcfd_fvm_plan* p, long batch, const char* what) {
     return 0;
 }
 
+// a bundle plan steps whole bundles, 1 + K fields per sample, and every pass but the stage kernel puts the field index in
+// gridDim.z (cell_grid): checked by every entry point that takes a bundle before it touches the device, and by the stage launcher
+constexpr long kMaxGridZ = 65535;
+
+int check_bundle_batch(const tcfd_fvm_plan* p, long batch, const char* what) {
+    if (!p->bundle) return 0;
+    if (batch % (1 + (long)p->bundle))
+        return FAIL(TCFD_EINVAL, "%s: batch %ld on a bundle plan of %d tangents, which takes whole bundles (batch = (1 + %d) B)", what,
+                    batch, p->bundle, p->bundle);
+    if (batch > kMaxGridZ)
+        return FAIL(TCFD_EINVAL, "%s: %ld fields on a bundle plan of %d tangents: the launch grids take at most %ld fields (state and "
+                                 "tangents together) in one call", what, batch, p->bundle, kMaxGridZ);
+    return 0;
+}
+
 template <typename T>
 int stage_launch(const tcfd_fvm_plan* p, const void* ux, const void* uy, const void* u0x, const void* u0y, void* kx, void* ky,
                  void* const* tx, void* const* ty, const double* c, const int* mode, int count, long batch, double dt,
                  hipStream_t st) {
+    if (int rc = check_bundle_batch(p, batch, "fvm stage")) return rc;
     if (int rc = check_ensemble_batch(p, batch, "fvm stage")) return rc;
     Targets<T> tg;
     tg.count = count;
@@ -876,8 +1109,19 @@ int stage_launch(const tcfd_fvm_plan* p, const void* ux, const void* uy, const v
     const size_t pair = (size_t)half_batch * p->n * p->n;
     // an ensemble plan: the EnsConst instantiations on the member table.  No call splits its batch, so sample 0 of a launch is member 0.
     const T* ens = (const T*)p->ens;
+    // a bundle plan: the bundle kernel over the B = batch / (1 + K) samples, tangent k (1 + k) B planes after the state
+    const long samples = batch / (1 + (long)p->bundle);
+    const size_t tan_stride = (size_t)samples * p->n * p->n;
 #define STAGE(SCHEME)                                                                                                      \
-    if (ens && p->tangent)                                                                                                 \
+    if (ens && p->bundle)                                                                                                  \
+        hipLaunchKernelGGL((k_fvm_stage_jvp_bundle<SCHEME, T, EnsConst<T>>), cell_grid(p->n, samples), kCellBlock, 0, st,  \
+                           (const T*)ux, (const T*)uy, (const T*)u0x, (const T*)u0y, (const T*)p->fx, (const T*)p->fy,     \
+                           (T*)kx, (T*)ky, tg, EnsConst<T>{stage_const<T>(p, dt), ens}, p->n, tan_stride, p->bundle);      \
+    else if (p->bundle)                                                                                                    \
+        hipLaunchKernelGGL((k_fvm_stage_jvp_bundle<SCHEME, T, StageConst<T>>), cell_grid(p->n, samples), kCellBlock, 0, st, \
+                           (const T*)ux, (const T*)uy, (const T*)u0x, (const T*)u0y, (const T*)p->fx, (const T*)p->fy,     \
+                           (T*)kx, (T*)ky, tg, stage_const<T>(p, dt), p->n, tan_stride, p->bundle);                        \
+    else if (ens && p->tangent)                                                                                                 \
         hipLaunchKernelGGL((k_fvm_stage_jvp<SCHEME, T, EnsConst<T>>), cell_grid(p->n, half_batch), kCellBlock, 0, st,      \
                            (const T*)ux, (const T*)uy, (const T*)u0x, (const T*)u0y, (const T*)p->fx, (const T*)p->fy,     \
                            (T*)kx, (T*)ky, tg, EnsConst<T>{stage_const<T>(p, dt), ens}, p->n, pair);                       \
@@ -1142,7 +1386,21 @@ int tcfd_fvm_plan_set_advection(tcfd_fvm_plan* p, int scheme) {
 int tcfd_fvm_plan_set_tangent(tcfd_fvm_plan* p, int on) {
     if (on != 0 && on != 1) return FAIL(TCFD_EINVAL, "fvm_plan_set_tangent: on = %d (0: plain plan, 1: tangent plan)", on);
     if (!p) return FAIL(TCFD_EINVAL, "fvm_plan_set_tangent: null plan");
+    if (on && p->bundle)
+        return FAIL(TCFD_EINVAL, "fvm_plan_set_tangent: the plan is a bundle plan of %d tangents (tcfd_fvm_plan_set_tangent_bundle); "
+                                 "clear the bundle first", p->bundle);
     p->tangent = on;
+    return 0;
+}
+
+int tcfd_fvm_plan_set_tangent_bundle(tcfd_fvm_plan* p, int ntangents) {
+    if (!p) return FAIL(TCFD_EINVAL, "fvm_plan_set_tangent_bundle: null plan");
+    if (ntangents < 0 || ntangents > TCFD_FVM_MAX_TANGENTS)
+        return FAIL(TCFD_EINVAL, "fvm_plan_set_tangent_bundle: ntangents = %d outside 0 .. %d (0: no bundle)", ntangents,
+                    TCFD_FVM_MAX_TANGENTS);
+    if (ntangents && p->tangent)
+        return FAIL(TCFD_EINVAL, "fvm_plan_set_tangent_bundle: the plan is a tangent plan (tcfd_fvm_plan_set_tangent); clear it first");
+    p->bundle = ntangents;
     return 0;
 }
 
@@ -1190,6 +1448,7 @@ int tcfd_fvm_explicit_terms(const tcfd_fvm_plan* p, const void* ux, const void* 
     if (!p || !ux || !uy || !kx || !ky || batch <= 0) return FAIL(TCFD_EINVAL, "fvm_explicit_terms: bad argument");
     if (p->tangent && batch % 2)
         return FAIL(TCFD_EINVAL, "fvm_explicit_terms: batch %ld on a tangent plan, which takes pairs (batch = 2 B)", batch);
+    if (int rcb = check_bundle_batch(p, batch, "fvm_explicit_terms")) return rcb;
     if (int rce = check_ensemble_batch(p, batch, "fvm_explicit_terms")) return rce;
     return stage_launch(p, ux, uy, ux, uy, kx, ky, nullptr, nullptr, nullptr, nullptr, 0, batch, dt, (hipStream_t)stream);
 }
@@ -1212,6 +1471,7 @@ int tcfd_fvm_step(const tcfd_fvm_plan* p, const void* ux_in, const void* uy_in, 
         return FAIL(TCFD_EINVAL, "fvm_step: bad argument");
     if (p->tangent && batch % 2)
         return FAIL(TCFD_EINVAL, "fvm_step: batch %ld on a tangent plan, which takes pairs (batch = 2 B)", batch);
+    if (int rcb = check_bundle_batch(p, batch, "fvm_step")) return rcb;
     if (int rce = check_ensemble_batch(p, batch, "fvm_step")) return rce;
     if (nstages < 1 || nstages > MAXT) return FAIL(TCFD_EINVAL, "fvm_step: %d stages (1 .. %d supported)", nstages, MAXT);
     for (int i = 0; i < nstages; ++i)
@@ -1279,6 +1539,7 @@ int tcfd_fvm_explicit_terms_vjp(const tcfd_fvm_plan* p, const void* ux, const vo
     if (!p || !ux || !uy || !gx || !gy || !out_x || !out_y || batch <= 0)
         return FAIL(TCFD_EINVAL, "fvm_explicit_terms_vjp: bad argument");
     if (p->tangent) return FAIL(TCFD_EINVAL, "fvm_explicit_terms_vjp: a tangent plan (forward over reverse is not provided)");
+    if (p->bundle) return FAIL(TCFD_EINVAL, "fvm_explicit_terms_vjp: a bundle plan (forward over reverse is not provided)");
     if (int rce = check_ensemble_batch(p, batch, "fvm_explicit_terms_vjp")) return rce;
     if (out_x == gx || out_x == gy || out_y == gx || out_y == gy || out_x == ux || out_x == uy || out_y == ux || out_y == uy)
         return FAIL(TCFD_EINVAL, "fvm_explicit_terms_vjp: the output may not alias an input (the stencil reads neighbours)");
@@ -1296,6 +1557,7 @@ int tcfd_fvm_step_vjp(const tcfd_fvm_plan* p, const void* saved, const void* gx,
     if (!p || !gx || !gy || !out_x || !out_y || batch <= 0 || steps < 0 || (steps > 0 && !saved) || !b || (nstages > 1 && !a))
         return FAIL(TCFD_EINVAL, "fvm_step_vjp: bad argument");
     if (p->tangent) return FAIL(TCFD_EINVAL, "fvm_step_vjp: a tangent plan (forward over reverse is not provided)");
+    if (p->bundle) return FAIL(TCFD_EINVAL, "fvm_step_vjp: a bundle plan (forward over reverse is not provided)");
     if (int rce = check_ensemble_batch(p, batch, "fvm_step_vjp")) return rce;
     if (nstages < 1 || nstages > MAXT) return FAIL(TCFD_EINVAL, "fvm_step_vjp: %d stages (1 .. %d supported)", nstages, MAXT);
     for (int i = 0; i < nstages; ++i)

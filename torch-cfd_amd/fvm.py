@@ -25,6 +25,12 @@ state through the tangent instantiation of the stage kernel (``k_fvm_stage_jvp``
 ``pressure_projection`` / ``PressureProjection.forward`` or ``get_trajectory_fvm`` runs the same calls; a component without a
 tangent counts as a zero tangent.  Forward over reverse is not provided.
 
+Tangent bundles: ``explicit_terms_jvp_bundle(u, dV, dt)`` and ``tangent_bundle_step(u, dV, dt, steps)`` carry K perturbations
+``dV[k]`` of ONE state through the bundle instantiation of the stage kernel (``k_fvm_stage_jvp_bundle``) on a bundle plan
+(``tcfd_fvm_plan_set_tangent_bundle``) that steps the stack ``[u; dV[0]; ..; dV[K-1]]`` in one library call: the state's loads,
+explicit terms, flux intermediates and projections are done once, not K times, and member k has the bits of
+``tangent_step(u, dV[k])``.  ``orthonormalize_velocity_tangents`` is the QR step between such calls.
+
 Ensembles: ``viscosity`` / ``drag`` / ``forcing_scale`` given per sample (a length-B sequence or a ``(B, 1, 1)`` tensor) make the
 equation an ENSEMBLE of B members.  Component ``b`` of a ``(B, n, n)`` state then runs with member ``b``'s values in every call
 above that evaluates the explicit terms -- stepping, ``explicit_terms``, the tangent-linear calls and dual numbers, and reverse
@@ -97,6 +103,60 @@ def _jvp_pairs(u, du, n: int, what: str):
         raise NotImplementedError(f"{what}: forward mode over reverse mode is not implemented -- the state or its tangent "
                                   "requires grad in grad mode; detach them or differentiate with the reverse-mode path alone")
     return (ux, uy), (dux, duy)
+
+
+def _bundle_pairs(u, dV, n: int, what: str):
+    """The checks the tangent-bundle entry points run before any device call: a bundle ``dV = (dVx, dVy)`` has components of
+    shape ``(K,) + ux.shape`` with K >= 1 (ValueError), then those of ``_jvp_pairs``.  Returns ``((ux, uy), (dVx, dVy), K)``."""
+    ux, uy = _as_pair(u)
+    dvx, dvy = _as_pair(dV)
+    if dvx.ndim != ux.ndim + 1 or tuple(dvx.shape[1:]) != tuple(ux.shape):
+        raise ValueError(f"{what}: a bundle of K tangents has components of shape (K,) + {tuple(ux.shape)}, the state's shape "
+                         f"behind the member index; got {tuple(dvx.shape)}")
+    K = int(dvx.shape[0])
+    if not 1 <= K <= _lib.TCFD_FVM_MAX_TANGENTS:
+        raise ValueError(f"{what}: a bundle of K = {K} tangents; K runs from 1 to {_lib.TCFD_FVM_MAX_TANGENTS}")
+    _jvp_pairs((ux, uy), (dvx[0], dvy[0]), n, what)
+    if torch.is_grad_enabled() and (dvx.requires_grad or dvy.requires_grad):
+        raise NotImplementedError(f"{what}: forward mode over reverse mode is not implemented -- the bundle requires grad in "
+                                  "grad mode; detach it or differentiate with the reverse-mode path alone")
+    return (ux, uy), (dvx, dvy), K
+
+
+def orthonormalize_velocity_tangents(dV) -> Tuple[Tuple[torch.Tensor, torch.Tensor], torch.Tensor]:
+    """QR of a bundle of velocity tangents in the cell-sum inner product ``<a, b> = sum (a_x b_x + a_y b_y)``: the
+    re-orthonormalisation of Benettin's method (Lyapunov spectra), of subspace and block-Krylov iterations; the finite-volume
+    counterpart of ``spectral.orthonormalize_tangents``.
+
+    ``dV = (dVx, dVy)``: components of shape ``(K, n, n)`` or ``(K, B, n, n)`` -- the bundle ``tangent_bundle_step`` carries.
+    Returns ``((Qx, Qy), R)``: Q of ``dV``'s shape with ``<Q[j], Q[k]> = delta_jk`` per sample, and ``R`` of shape ``(K, K)`` /
+    ``(B, K, K)``, upper triangular with a positive diagonal, ``dV[k] = sum_j Q[j] R[j, k]``.  The sum of ``log R[k, k]`` over the
+    re-orthonormalisations, divided by the time, is the k-th Lyapunov exponent.  A Householder QR (``torch.linalg.qr``) of the
+    ``(2 n^2, K)`` matrices, so nearly parallel tangents -- the normal case, every tangent leans towards the leading vector --
+    lose no orthogonality.  Plain tensor arithmetic on the tensors' device (the CPU included), run once per some tens of steps;
+    not a kernel of the library."""
+    try:
+        dvx, dvy = _as_pair(dV)
+    except (TypeError, AttributeError) as e:
+        raise ValueError(f"orthonormalize_velocity_tangents: expected a pair (dVx, dVy) of tensors: {e}") from None
+    if dvx.dim() not in (3, 4) or not dvx.is_floating_point() or dvx.shape[-1] != dvx.shape[-2]:
+        raise ValueError("orthonormalize_velocity_tangents: expected real components of shape (K, n, n) or (K, B, n, n), got "
+                         f"{tuple(dvx.shape)} {dvx.dtype}")
+    single = dvx.dim() == 3
+    ax, ay = (c.unsqueeze(1) if single else c for c in (dvx, dvy))
+    K, B, n, _ = ax.shape
+    if not 1 <= K <= 2 * n * n:
+        raise ValueError(f"orthonormalize_velocity_tangents: {K} tangents in a space of {2 * n * n} dimensions")
+    M = torch.stack([ax, ay], dim=2).reshape(K, B, 2 * n * n).permute(1, 2, 0)                # (B, 2 n^2, K); rows: (x / y, i, j)
+    Q, R = torch.linalg.qr(M, mode="reduced")
+    sign = torch.where(torch.diagonal(R, dim1=-2, dim2=-1) < 0, -1.0, 1.0).to(dvx.dtype)      # (B, K): positive diagonal
+    Q = Q * sign.unsqueeze(-2)
+    R = R * sign.unsqueeze(-1)
+    Q = Q.permute(2, 0, 1).reshape(K, B, 2, n, n)
+    qx, qy = Q[:, :, 0].contiguous(), Q[:, :, 1].contiguous()
+    if single:
+        return (qx[:, 0], qy[:, 0]), R[0]
+    return (qx, qy), R
 
 
 def _check_periodic(bcs) -> None:
@@ -263,12 +323,19 @@ class RKStepper(nn.Module):
 
 
 # ----------------------------------------------------------------------------- device plan
+def _require_entry(lib, name: str, what: str) -> None:
+    """An entry point added without a new ABI number: a library built before it loads, but lacks it."""
+    if not hasattr(lib, name):
+        raise _lib.TcfdError(f"{_lib.LIB_PATH} was built before {what} ({name}) were added: rebuild it with "
+                             "torch_cfd_amd._lib.build_library(force=True)")
+
+
 class _FvmPlan:
     """Owns one ``tcfd_fvm_plan`` (inverse-eigenvalue and forcing tables) + a workspace."""
 
     def __init__(self, n: int, dtype: torch.dtype, device: torch.device, h: float, nu: float, drag: float,
                  inverse: torch.Tensor, force: Optional[Tuple[torch.Tensor, torch.Tensor]],
-                 scheme: int = _lib.TCFD_FVM_VAN_LEER, tangent: bool = False, members=None):
+                 scheme: int = _lib.TCFD_FVM_VAN_LEER, tangent: bool = False, members=None, bundle: int = 0):
         self.lib = _lib.load()
         self.n, self.dtype, self.device = n, dtype, torch.device(device)
         if self.device.type != "cuda":
@@ -294,7 +361,11 @@ class _FvmPlan:
         self.tangent = bool(tangent)   # a tangent plan steps pairs [u; du]: its calls go through the *_pair methods below
         if self.tangent:
             _lib.check(self.lib.tcfd_fvm_plan_set_tangent(handle, 1), "tcfd_fvm_plan_set_tangent")
-        self.members = 0   # B of an ensemble plan: every call but project then takes B fields (a tangent plan: 2 B)
+        self.bundle = int(bundle)   # K > 0: a bundle plan steps [u; du_0 .. du_{K-1}]: its calls go through the *_bundle methods
+        if self.bundle:
+            _require_entry(self.lib, "tcfd_fvm_plan_set_tangent_bundle", "tangent bundles")
+            _lib.check(self.lib.tcfd_fvm_plan_set_tangent_bundle(handle, self.bundle), "tcfd_fvm_plan_set_tangent_bundle")
+        self.members = 0   # B of an ensemble plan: every call but project then takes B fields (a tangent plan: 2 B; a bundle: (1 + K) B)
         if members is not None:
             self.set_ensemble(*members)
 
@@ -388,6 +459,25 @@ class _FvmPlan:
 
     def project_pair(self, ux, uy, dux, duy):
         return self._split(*self.project(self._stack(ux, dux), self._stack(uy, duy)), ux.shape)
+
+    # ---- a bundle plan: the state and its K tangents stacked, [u; du_0; ..; du_{K-1}], tangent k (1 + k) B fields in
+    def _stack_bundle(self, u, dv):
+        return torch.cat([u.reshape((-1,) + u.shape[-2:]), dv.reshape((-1,) + dv.shape[-2:])])
+
+    def _split_bundle(self, ox, oy, shape):
+        b = ox.shape[0] // (1 + self.bundle)
+        tshape = (self.bundle,) + tuple(shape)
+        return (ox[:b].reshape(shape), oy[:b].reshape(shape)), (ox[b:].reshape(tshape), oy[b:].reshape(tshape))
+
+    def explicit_terms_bundle(self, ux, uy, dvx, dvy, dt: float):
+        """``((kx, ky), (dKx, dKy))`` = ``(F(u), [J_F(u) dV[k]])``, one launch of the bundle stage kernel."""
+        assert self.bundle and dvx.shape[0] == self.bundle
+        return self._split_bundle(*self.explicit_terms(self._stack_bundle(ux, dvx), self._stack_bundle(uy, dvy), dt), ux.shape)
+
+    def step_bundle(self, ux, uy, dvx, dvy, dt: float, a: Sequence[float], b: Sequence[float], steps: int):
+        """``steps`` RK steps of the state and of its K tangents in one library call."""
+        assert self.bundle and dvx.shape[0] == self.bundle
+        return self._split_bundle(*self.step(self._stack_bundle(ux, dvx), self._stack_bundle(uy, dvy), dt, a, b, steps), ux.shape)
 
     # ---- reverse mode (fvm_autograd.py)
     def explicit_terms_vjp(self, ux, uy, gx, gy, dt: float):
@@ -565,6 +655,7 @@ class NavierStokes2DFVMProjection(nn.Module):
         self._convect_plans: Dict[tuple, _FvmPlan] = {}
         self._tangent_plans: Dict[tuple, _FvmPlan] = {}           # the tangent variants of the two: plain calls never see them
         self._convect_tangent_plans: Dict[tuple, _FvmPlan] = {}
+        self._bundle_plans: Dict[tuple, Dict[int, _FvmPlan]] = {}  # key -> {K: the bundle plan of K tangents}
 
     def _force_tables(self):
         """(fx, fy) / density at the staggered offsets, sampled once per plan (the forcing is state independent)."""
@@ -623,6 +714,23 @@ class NavierStokes2DFVMProjection(nn.Module):
             plans[key] = plan
         return plan
 
+    def _bundle_plan(self, dtype, device, K: int) -> _FvmPlan:
+        """The bundle plan of K tangents per state (``tcfd_fvm_plan_set_tangent_bundle``), cached per K under the key of
+        ``_plans`` / ``_tangent_plans``; a changed key drops the plans of every K."""
+        key = self._plan_key(dtype, device)
+        per_k = self._bundle_plans.get(key)
+        if per_k is None:
+            self._bundle_plans.clear()
+            per_k = self._bundle_plans[key] = {}
+        plan = per_k.get(K)
+        if plan is None:
+            members = self._members()
+            nu, drag = (members[0][0], members[1][0]) if members else (self.viscosity / self.density, self.drag)
+            plan = per_k[K] = _FvmPlan(self.grid.shape[0], dtype, device, _square_step(self.grid), nu, drag,
+                                       self._projection.solver.inverse, self._force_tables(), self.advection.scheme,
+                                       members=members, bundle=K)
+        return plan
+
     def _convect_plan(self, dtype, device, tangent: bool = False) -> _FvmPlan:
         """The plan of the advection term alone: no viscosity, no drag, no forcing.  A second full plan, created at the first
         ``convect`` call: it uploads the inverse-eigenvalue table again and owns a transform plan it never runs, and a
@@ -674,6 +782,29 @@ class NavierStokes2DFVMProjection(nn.Module):
         ``((ux, uy), (dux, duy))`` with ``du_new = d(u_new)/d(u) . du`` (the tangent-linear model), all stages and
         projections of all steps in one library call.  ``(n, n)`` or ``(B, n, n)`` components."""
         return self._tangent_steps(u, du, dt, steps, self.solver)
+
+    # -- a bundle of K tangents per state on the bundle stage kernel (a bundle plan, tcfd_fvm_plan_set_tangent_bundle)
+    def explicit_terms_jvp_bundle(self, u, dV, dt: float):
+        """``((kx, ky), (dKx, dKy))``: the explicit terms ``F(u)`` and ``J_F(u) dV[k]`` for the K members of the bundle
+        ``dV = (dVx, dVy)`` (components of shape ``(K,) + ux.shape``), one fused launch.  Member k has the bits of
+        ``explicit_terms_jvp(u, dV[k], dt)``."""
+        (ux, uy), (dvx, dvy), K = _bundle_pairs(u, dV, self.grid.shape[0], "explicit_terms_jvp_bundle")
+        self._check_members(ux, "explicit_terms_jvp_bundle")
+        return self._bundle_plan(ux.dtype, ux.device, K).explicit_terms_bundle(ux, uy, dvx, dvy, dt)
+
+    def tangent_bundle_step(self, u, dV, dt: float, steps: int = 1):
+        """``steps`` steps of the equation's solver on the state AND on K perturbations of it, ``dV = (dVx, dVy)`` with
+        components of shape ``(K,) + ux.shape``: returns ``((ux, uy), (dUx, dUy))`` with ``dU[k] = d(u_new)/d(u) . dV[k]``, all
+        stages and projections of all steps in one library call.  What K calls of ``tangent_step`` on the same state compute --
+        member k has their bits -- with the state's share of every stage and its projections done once (Lyapunov spectra with
+        ``orthonormalize_velocity_tangents``, block Krylov, several Gauss-Newton directions)."""
+        if self.solver is None:
+            raise ValueError("NavierStokes2DFVMProjection: no RKStepper (pass solver=RKStepper.from_method(...))")
+        (ux, uy), (dvx, dvy), K = _bundle_pairs(u, dV, self.grid.shape[0], "tangent_bundle_step")
+        self._check_members(ux, "tangent_bundle_step")
+        self.solver._check_no_grad()
+        a, b = self.solver.weights(dt)
+        return self._bundle_plan(ux.dtype, ux.device, K).step_bundle(ux, uy, dvx, dvy, dt, a, b, steps)
 
     def explicit_terms(self, u, dt: float):
         ux, uy = _as_pair(u)
